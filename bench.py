@@ -5,6 +5,15 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
 For N > 1 the driver launches one process per GPU with torch.distributed.run
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env, RCCL backend).
 
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`, the workload's `config`).  `--dump-outputs DIR`
+writes the last timed step's results as .npy files (dump_outputs below; the
+inputs are seeded, so two builds can be compared output for output).
+Everything else described here -- `roofline`, `stage_ms_per_step`,
+`host_fetch`, latency, `cpu_baseline*`, `keypoint_stages`, `gather`,
+`configs` -- is measured after the timed steps by passes of its own and only
+with `--full`, which adds those fields to the same line.
+
 Workload (BASELINE.json configs[3], per GPU): every rank owns its own batch of
 `--frames` (default 128) synthetic 1920x1080 u8 frames generated on its GPU
 (seeded, sift-features_amd/synth.py) -- images are independent, so the batch
@@ -60,6 +69,11 @@ def parse():
     p.add_argument("--width", type=int, default=1920)
     p.add_argument("--height", type=int, default=1080)
     p.add_argument("--chunk", type=int, default=0, help="frames per pipeline chunk (0 = auto)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other measurement (stage timing and roofline passes, "
+                        "host fetch, latency, CPU baselines, the other configs, JPEG end to end, N > 1 gather)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's results (rank 0) as DIR/<name>.npy")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-latency", action="store_true")
@@ -193,6 +207,76 @@ def run_jpeg_e2e(pkg, synth, device_index, n, W, H, steps, threads):
                     "JPEGs in host memory, results kept on the device"}
 
 
+DUMP_KEYPOINT_ROWS = 1_200_000  # 24 MB of f32 (+ 9.6 MB of row indices when sampled)
+DUMP_DESCRIPTOR_ROWS = 56_000  # 28.7 MB as f32
+
+
+def sample_rows(rng, n, cap):
+    """Every row of n when n <= cap, else cap of them drawn without replacement, ascending."""
+    return np.sort(rng.choice(n, cap, replace=False)) if n > cap else np.arange(n)
+
+
+def dump_outputs(path, shard, ctx, offsets):
+    """--dump-outputs: what the caller of the timed step holds after the last
+    one -- the per-frame offsets it returned and the keypoints / descriptors
+    it left in HBM -- as float32 / float64 .npy files, under 64 MB in all:
+      offsets.npy          (frames + 1,) f64, rows of frame i = [offsets[i], offsets[i + 1])
+      keypoints.npy        (n, 5) f32 (x, y, size, angle, response), frame order
+      descriptors.npy      (m, 128) f32, the u8 descriptors of rows descriptor_rows
+      descriptor_rows.npy  (m,) f64 row indices into the n results
+      keypoint_rows.npy    only when n > DUMP_KEYPOINT_ROWS: keypoints.npy then holds these rows
+    Rows are sampled without replacement by np.random.default_rng(0), sorted,
+    so equal result counts give equal samples."""
+    import torch
+    k_dev, d_dev = shard.device_results(ctx)
+    torch.cuda.synchronize()
+    n = int(k_dev.shape[0])
+    assert n == int(offsets[-1]), (n, int(offsets[-1]))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "offsets.npy"), np.asarray(offsets, dtype=np.float64))
+    rng = np.random.default_rng(0)
+    drows = sample_rows(rng, n, DUMP_DESCRIPTOR_ROWS)
+    idx = torch.as_tensor(drows, dtype=torch.int64, device=d_dev.device)
+    np.save(os.path.join(path, "descriptors.npy"), d_dev[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "descriptor_rows.npy"), drows.astype(np.float64))
+    kps = k_dev.cpu().numpy().astype(np.float32)
+    if n > DUMP_KEYPOINT_ROWS:
+        krows = sample_rows(rng, n, DUMP_KEYPOINT_ROWS)
+        kps = kps[krows]
+        np.save(os.path.join(path, "keypoint_rows.npy"), krows.astype(np.float64))
+    np.save(os.path.join(path, "keypoints.npy"), kps)
+
+
+def headline(args, world, B, W, H, dt_max, total_kp, total_frames):
+    """The result line of every run: the timed steps' figures and what they ran on."""
+    n_oct = int(round(np.log2(min(2 * W, 2 * H)) - 2)) + 1
+    return {
+        "metric": METRIC,
+        "value": total_kp / dt_max,
+        "unit": "keypoints/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt_max / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded procedural blob frames generated on device, synth.py)",
+        "config": {"workload": f"batch of {B} x {W}x{H} u8 frames per GPU (configs[3] shard), full sift()",
+                   "frames_per_gpu": B, "frame": f"{W}x{H}", "octaves": n_oct, "profile": "opencv",
+                   "parallelism": f"dp{world} (frames sharded, no collective)",
+                   "chunking": (f"--chunk {args.chunk}" if args.chunk else
+                                "auto (path option chunk_mode, default 1: as few chunks as ~64 GB of pyramid "
+                                "allows; 128 x 1080p runs as one chunk)"),
+                   **({"path_options": dict(PATH_OPTS)} if PATH_OPTS else {}),
+                   **({"rehearsal": "every rank on cuda:0, gloo transport: not a measurement"}
+                      if args.rehearse_one_gpu else {})},
+        "frames_per_s": total_frames / dt_max,
+        "keypoints_per_frame": total_kp / max(1.0, total_frames),
+    }
+
+
 def main():
     args = parse()
     import torch
@@ -255,6 +339,20 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
 
+    dt_max, total_kp, total_frames = shard.reduce_run(dt, n_kp, B * args.steps, dist if world > 1 else None)
+    head = headline(args, world, B, W, H, dt_max, total_kp, total_frames)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shard, ctx, last["offs"])
+
+    # A plain run ends here; everything below is --full.
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # Stage timing pass: the same steps with the chunks run one after another
     # (one pipeline lane), so the HIP-event time of each stage -- and the
     # pyramid roofline below -- is its kernels' own, not shared with the
@@ -304,8 +402,6 @@ def main():
         "note": "samples = patch positions / rotated-region samples the kernels evaluate (rank 0, one step, "
                 "sift_mi_set_sample_counting); times from the serialised stage-timing pass",
     }
-
-    dt_max, total_kp, total_frames = shard.reduce_run(dt, n_kp, B * args.steps, dist if world > 1 else None)
 
     # N > 1: the keypoint gather of the throughput path -- every rank's
     # device-resident results to rank 0 over RCCL (shard.gather_device_results:
@@ -460,31 +556,8 @@ def main():
         pass
 
     if rank == 0:
-        n_oct = int(round(np.log2(min(2 * W, 2 * H)) - 2)) + 1
         out = {
-            "metric": METRIC,
-            "value": total_kp / dt_max,
-            "unit": "keypoints/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt_max / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (seeded procedural blob frames generated on device, synth.py)",
-            "config": {"workload": f"batch of {B} x {W}x{H} u8 frames per GPU (configs[3] shard), full sift()",
-                       "frames_per_gpu": B, "frame": f"{W}x{H}", "octaves": n_oct, "profile": "opencv",
-                       "parallelism": f"dp{world} (frames sharded, no collective)",
-                       "chunking": (f"--chunk {args.chunk}" if args.chunk else
-                                    "auto (path option chunk_mode, default 1: as few chunks as ~64 GB of pyramid "
-                                    "allows; 128 x 1080p runs as one chunk)"),
-                       **({"path_options": dict(PATH_OPTS)} if PATH_OPTS else {}),
-                       **({"rehearsal": "every rank on cuda:0, gloo transport: not a measurement"}
-                          if args.rehearse_one_gpu else {})},
-            "frames_per_s": total_frames / dt_max,
-            "keypoints_per_frame": total_kp / max(1.0, total_frames),
+            **head,
             "stage_ms_per_step": {k: st[k] / args.steps for k in
                                   ("pyramid_ms", "detect_ms", "orient_ms", "order_ms", "descriptor_ms", "total_ms")},
             "serial_lane_ms_per_step": serial_ms,

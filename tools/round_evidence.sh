@@ -2,9 +2,10 @@
 # Round evidence (run via gpurun): the default bench line, then the round
 # profile (trace + PMC passes) of the same workload
 cd "$GRAFT_REPO_ROOT" || exit 2
-mkdir -p gpurun_out
-timeout -k 10 600 python3 bench.py > gpurun_out/r06_bench.log 2>&1 || { tail -20 gpurun_out/r06_bench.log; exit 1; }
-grep '^{' gpurun_out/r06_bench.log | python3 -c "
+LOG=${OUT:-bench_out}/r06_bench.log  # where the bench log goes
+mkdir -p "$(dirname "$LOG")"
+timeout -k 10 600 python3 bench.py --full > "$LOG" 2>&1 || { tail -20 "$LOG"; exit 1; }
+grep '^{' "$LOG" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('value', d['value'], 'ms', d['ms_per_step'], 'frac', d['roofline']['frac'], 'stages', d['stage_ms_per_step'])
