@@ -5,6 +5,7 @@ import this module.  It restates /root/reference/src/lib.rs (see
 oracle/sift_oracle.c for the per-function citations); it is the checker,
 never the thing measured or shipped.
 """
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -74,8 +75,27 @@ def lib():
         L.oracle_octave_sigmas.argtypes = [vp]
         L.oracle_seed_sigma.restype = f64
         L.oracle_match.argtypes = [vp, i32, vp, i32, i32, vp, vp]
+        L.oracle_set_variant.argtypes = [i32]
+        L.oracle_set_variant.restype = None
         _lib = L
     return _lib
+
+
+VARIANT_STRICT_EXTREMUM = 256
+VARIANT_HALF_UP_BIN = 512
+VARIANT_F32_ATAN2 = 1024
+
+
+@contextlib.contextmanager
+def set_variant(bits):
+    """Run the oracle with arithmetic-variant `bits` (oracle_set_variant in
+    sift_oracle.c) inside the `with` block; always back to 0 afterwards.
+    Bits 256, 512 and 1024 are wrong on purpose (test use only)."""
+    lib().oracle_set_variant(int(bits))
+    try:
+        yield
+    finally:
+        lib().oracle_set_variant(0)
 
 
 def _u8(img):

@@ -152,7 +152,14 @@ static inline int reflect101(int p, int len) {
 }
 
 /* Arithmetic-variant switch for pinning experiments against the snapshots
- * (tools only; 0 = the restatement documented above). */
+ * (tools only; 0 = the restatement documented above).  Bits 1..128 are
+ * plausible alternative operation orders.  Bits 256, 512 and 1024 are WRONG ON
+ * PURPOSE, TEST USE ONLY: each breaks one equality-dependent decision so that
+ * tests/test_patterns_cpu.py can show which inputs notice (DESIGN.md,
+ * "Structured patterns"):
+ *   256   strict comparisons in is_extremum (> / < for >= / <=)
+ *   512   orientation bin by floorf(raw_bin + 0.5f) for roundf (half away)
+ *   1024  orientation angle by f32 atan2f for (float)atan2(double) */
 static int g_variant = 0;
 void oracle_set_variant(int v) { g_variant = v; }
 
@@ -553,6 +560,14 @@ static int is_extremum(const float* prev, const float* curr, const float* next, 
     static const int dxv[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
     if (fabsf(val) <= threshold) return 0;
     const float* sl[3] = {curr, prev, next};
+    if (g_variant & 256) { /* wrong on purpose: strict */
+        for (int s = 0; s < 3; s++)
+            for (int i = 0; i < 8; i++) {
+                const float nb = sl[s][c + (ptrdiff_t)dyv[i] * w + dxv[i]];
+                if (!(val > 0.0f ? val > nb : val < nb)) return 0;
+            }
+        return val > 0.0f ? val > fmaxf(prev[c], next[c]) : val < fminf(prev[c], next[c]);
+    }
     if (val > 0.0f) {
         for (int s = 0; s < 3; s++)
             for (int i = 0; i < 8; i++)
@@ -674,9 +689,9 @@ void oracle_orientation_hist(const float* img, int w, int h, int x, int y, int r
             const float wexp = (float)(yp * yp + xp * xp) * gws;
             const float weight = expf(wexp);
             const float mag = sqrtf(dx * dx + dy * dy);
-            const float ori = (float)atan2((double)dy, (double)dx);
+            const float ori = (g_variant & 1024) ? atan2f(dy, dx) : (float)atan2((double)dy, (double)dx);
             const float raw_bin = bin_step * ori;
-            int bin = sat_i32(roundf(raw_bin));
+            int bin = sat_i32((g_variant & 512) ? floorf(raw_bin + 0.5f) : roundf(raw_bin));
             if (bin >= n_bins)
                 bin -= n_bins;
             else if (bin < 0)

@@ -161,16 +161,17 @@ def test_path_option_validation_and_restore(pkg):
 
 @pytest.mark.gpu
 def test_chunk_mode_results_equal(pkg):
-    """Automatic chunking mode 1 (as few chunks as memory allows: the five
-    640x480 frames in one chunk instead of 3 + 2 over both lanes) returns
-    the same keypoints and descriptors, frame for frame."""
+    """Automatic chunking mode 1 (the default; as few chunks as memory allows:
+    the five 640x480 frames in one chunk) returns the same keypoints and
+    descriptors, frame for frame, as mode 0 (3 + 2 over both lanes)."""
     import synth
     fr = synth.frames(5, 640, 480, seed0=40)
     c = pkg.Context(0, pkg.OpenCVProcessing)
     try:
-        ref = c.sift_batch(fr)
-        with c.path_options(chunk_mode=1):
-            got = c.sift_batch(fr)
+        assert c.path_option("chunk_mode") == 1
+        with c.path_options(chunk_mode=0):
+            ref = c.sift_batch(fr)
+        got = c.sift_batch(fr)
         assert len(ref) == len(got) == 5
         for a, b in zip(ref, got):
             assert np.array_equal(a.keypoints_array, b.keypoints_array)
