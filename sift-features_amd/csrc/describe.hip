@@ -351,21 +351,40 @@ __device__ __forceinline__ void describe_wave_exact(const float* __restrict__ im
 
 // Fast path (the default): lane-private 4x4x8 histograms.
 //
-// Lanes walk the compacted samples with stride 64 and add each sample's
+// Lanes walk the compacted samples (band walk, below) and add each sample's
 // interior contributions (cells 1..4 x 1..4; the reference discards the
 // border ring, src/lib.rs:951) into a private 128-bin slice of LDS (bin-major,
-// lane-minor layout: conflict-free) with plain read-add-write (LDS float atomics cost ~3 cycles per lane on gfx950,
+// lane-minor layout: conflict-free within a group of NS lanes) with plain read-add-write (LDS float atomics cost ~3 cycles per lane on gfx950,
 // tools/ubench_lds.hip); the 64 slices are then summed per bin.  Per-sample
 // arithmetic is the reference's; only the order of the bin additions differs,
 // so bins agree to f32 rounding and the u8 components to +-1 (the tolerance
 // tests/test_gpu_parity.py states).  describe_wave_exact is the bit-exact
 // alternative (sift_mi_set_exact_descriptors).
 //
-// kShare lanes share one slice (64 / kShare slices per wave): their updates
-// are issued group by group (lanes [g*S, (g+1)*S) in step g), so no two lanes
-// of a slice write in the same instruction.  Sharing trades LDS instructions
-// for LDS footprint -- 38.9 KB per wave at kShare = 1 (one wave per SIMD),
-// 19.5 KB at 2, 9.7 KB at 4 -- i.e. for occupancy.
+// kShare lanes share one slice (64 / kShare slices per wave; lane l: slice
+// l % NS, partners l ^ NS, ...).  Sharing trades LDS instructions for LDS
+// footprint -- 38.9 KB per wave at kShare = 1 (one wave per SIMD), 19.5 KB at
+// 2, 9.7 KB at 4 -- i.e. for occupancy.
+//
+// Band-interleaved walk: the compacted sample list is cut into kShare bands
+// of Q = ceil(total / kShare) samples and the lanes of slice-sharing group g
+// (lanes [g * NS, (g + 1) * NS)) walk band g, NS neighbouring samples per
+// step.  The partners of a slice are then a quarter of the window (~1.8
+// cells in rotated space) apart instead of NS places in one row-major list,
+// where a window row of ~NS samples put them one row apart in the same
+// column, i.e. in the same 2x2-cell footprint.
+//
+// One-pass scatter: all 64 lanes update corner by corner (read pair, packed
+// add, write pair in the same three instructions).  Two lanes of a slice may
+// not touch overlapping slots in one instruction: with the same corner in
+// every lane that needs two inside samples with the same footprint origin
+// (r1, q1) and |o0 - o0'| <= 1 (slot 8 keeps 7 and 0 apart; the dummy pairs
+// may collide, their sums are discarded).  Each iteration the lanes compare
+// their keys (origin * 10 + o0; per-band sentinels when not inside) with
+// their partners' through v_permlane{16,32}_swap; if any pair in the wave is
+// within 1 the iteration takes the four-round form instead (group by group,
+// lanes [g * NS, (g + 1) * NS) in round g, so no two lanes of a slice write
+// in the same instruction).
 //
 // Slice layout: 9 slots per interior cell (slot 8 aliases orientation 0 and is
 // folded into it at the end), so a sample's two orientation bins o0, o0 + 1 of
@@ -425,14 +444,44 @@ struct NoHook {
     __device__ void operator()() const {}
 };
 
+// Measurement hooks of the micro-benchmark (kAblate bit 5 only).
+struct DescProbe {
+    float* raw = nullptr;  // the wave's 128 bin sums before normalisation
+    uint32_t iters = 0, fallbacks = 0;  // sample-loop iterations, and those that took the four-round form
+};
+
+// a zero byte in v (exact for the lowest zero byte; none reported without one)
+__device__ __forceinline__ uint32_t zero_byte(uint32_t v) { return (v - 0x01010101u) & ~v & 0x80808080u; }
+
+// Whether this lane's packed key bytes p equal a slice partner's in any byte
+// position (partners: lanes ^32 at kShare 2; ^16, ^32, ^48 at kShare 4).  The
+// swaps leave both operands of a pair in one lane: (x ^ 32) after
+// v_permlane32_swap of p with itself, (x ^ 16) after v_permlane16_swap, and
+// rows {2, 3} broadcast over the 32-swapped rows {0, 1} for the two cross pairs.
+template <int kShare>
+__device__ __forceinline__ bool partner_key_match(uint32_t p) {
+    static_assert(kShare == 2 || kShare == 4, "partner exchange written for 2 or 4 lanes per slice");
+    const auto h = __builtin_amdgcn_permlane32_swap(p, p, false, false);  // [r0 r1 r0 r1], [r2 r3 r2 r3]
+    if constexpr (kShare == 2) return zero_byte(h[0] ^ h[1]) != 0;
+    const auto q = __builtin_amdgcn_permlane16_swap(p, p, false, false);       // [r0 r0 r2 r2], [r1 r1 r3 r3]
+    const auto c = __builtin_amdgcn_permlane16_swap(h[1], h[1], false, false);  // [r2 r2 r2 r2], [r3 r3 r3 r3]
+    // rows (0, 1) and (2, 3); rows {0, 1} against row 2; rows {0, 1} against row 3
+    return (zero_byte(q[0] ^ q[1]) | zero_byte(h[0] ^ c[0]) | zero_byte(h[0] ^ c[1])) != 0;
+}
+
 // `mid` runs between the sample loop and the final reduction (the caller
 // issues its next keypoint's loads there, hidden behind the reduction).
+//
+// kAblate (performance experiments only, tools/ubench_kernels.hip; 0 in the
+// product): bit 0 register sink instead of the slice updates, bit 1 replace
+// atan2, bit 2 replace exp, bit 3 replace the gradient loads, bit 4 the
+// four-round scatter in every iteration, bit 5 fill `probe`, bit 6 no samples.
 template <int kShare, int kAblate = 0, class Mid = NoHook>
 __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img, int pitch, int width, int height,
                                                    float xf, float yf, float scale, float orientation,
                                                    float sin_ori, float cos_ori, DescScratchFast<kShare>& sc,
                                                    uint8_t* __restrict__ out, int lane, Mid mid = Mid(),
-                                                   uint32_t* n_samples = nullptr) {
+                                                   uint32_t* n_samples = nullptr, DescProbe* probe = nullptr) {
     constexpr int NS = 64 / kShare;  // slices
     const int32_t x = (int32_t)sat_u32(roundf(xf));
     const int32_t y = (int32_t)sat_u32(roundf(yf));
@@ -455,12 +504,29 @@ __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img
     build_row_table<true>(sc.rowlo, sc.rowpre, radius, cos_s, sin_s, lane, 1 - x, width - 2 - x, 1 - y, height - 2 - y);
     const int total = (kAblate & 64) ? 0 : sc.rowpre[n];  // kAblate bit 6: no samples (per-keypoint overhead)
     if (n_samples) *n_samples += (uint32_t)total;
-    // Lane-strided samples: one load instruction touches ~64 neighbouring
-    // pixels (2-3 cache lines) instead of 64 scattered ones.  Each iteration
-    // takes two samples per lane (k, k + 64) -- packed math, independent
-    // chains for the ~2 waves per SIMD the LDS footprint allows -- and the
-    // gradient loads of the next two are in flight meanwhile.
+    // Band walk: lane (g, j) takes samples kb + j + NS * t of band g = [kb,
+    // kb + Q): one load instruction touches NS neighbouring pixels per group
+    // (kShare short runs instead of one of 64).  Each iteration takes two
+    // samples per lane (t, t + 1) -- packed math, independent chains -- and
+    // the gradient loads of the next two are in flight meanwhile.  Lanes past
+    // the end of their band idle (their loads are clamped to the last sample).
+    const int Q = (total + kShare - 1) / kShare;
+    const int kb = grp * Q, kj = lane & (NS - 1);
+    // per-lane row cursor: a bounded search for the first sample's row (the
+    // first row r with rowpre[r + 1] > k; n <= 79 < 2^7), then forward steps
     int row = 0;
+    if (kShare > 1 && total > 0) {
+        const int k = min(kb + kj, total - 1);
+        int lo = 0, hi = n - 1;
+#pragma unroll
+        for (int s = 0; s < 7; s++) {
+            const int m = (lo + hi) >> 1;
+            const bool gt = sc.rowpre[m + 1] > k;
+            hi = gt ? m : hi;
+            lo = gt ? lo : m + 1;
+        }
+        row = lo;
+    }
     auto locate = [&](int k, int& xi, int& yi) {
         while (sc.rowpre[row + 1] <= k) row++;
         yi = row - radius;
@@ -489,17 +555,17 @@ __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img
     if (total > 0) {
 #pragma unroll
         for (int u = 0; u < 2; u++) {
-            locate(min(lane + 64 * u, total - 1), nxi[u], nyi[u]);
+            locate(min(kb + kj + NS * u, total - 1), nxi[u], nyi[u]);
             if (!(kAblate & 8)) fetch(nxi[u], nyi[u], nl[u], nr[u], nu[u], nd[u]);
         }
     }
-    for (int k = lane; k - lane < total; k += 128) {
+    for (int t = kj; t - kj < Q; t += 2 * NS) {  // t: this lane's place in its band
         const int xi[2] = {nxi[0], nxi[1]}, yi[2] = {nyi[0], nyi[1]};
         const f2v gl = {nl[0], nl[1]}, gr = {nr[0], nr[1]}, gu = {nu[0], nu[1]}, gd = {nd[0], nd[1]};
-        if (k - lane + 128 < total) {
+        if (t - kj + 2 * NS < Q) {
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                locate(min(k + 128 + 64 * u, total - 1), nxi[u], nyi[u]);
+                locate(min(kb + t + 2 * NS + NS * u, total - 1), nxi[u], nyi[u]);
                 if (!(kAblate & 8)) fetch(nxi[u], nyi[u], nl[u], nr[u], nu[u], nd[u]);
             }
         }
@@ -512,8 +578,9 @@ __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img
         bool inside[2];
 #pragma unroll
         for (int u = 0; u < 2; u++)
-            inside[u] = k + 64 * u < total && row_bin[u] > -0.5f && row_bin[u] < (float)kDescHist + 0.5f &&
-                        col_bin[u] > -0.5f && col_bin[u] < (float)kDescHist + 0.5f;
+            inside[u] = t + NS * u < Q && kb + t + NS * u < total && row_bin[u] > -0.5f &&
+                        row_bin[u] < (float)kDescHist + 0.5f && col_bin[u] > -0.5f &&
+                        col_bin[u] < (float)kDescHist + 0.5f;
         f2v dx, dy;
         if (kAblate & 8) {
             dx = fx * 0.01f + 0.001f;
@@ -553,6 +620,7 @@ __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img
         const f2v c011 = c01 * ori_frac, c010 = c01 - c011;
         const f2v c001 = c00 * ori_frac, c000 = c00 - c001;
         int a[2][4];
+        uint32_t keys = 0;  // 2 bytes per sample: key >> 1, (key + 1) >> 1 -- keys within 1 share one of them
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int r1 = (int)row_floor[u] + 1, q1 = (int)col_floor[u] + 1;  // 0..4
@@ -568,6 +636,11 @@ __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img
             a[u][1] = ((rv1 && qv2) ? base + 9 : 146) * NS;
             a[u][2] = ((rv2 && qv1) ? base + 36 : 148) * NS;
             a[u][3] = ((rv2 && qv2) ? base + 45 : 150) * NS;
+            // hazard key (r1 * 5 + q1) * 10 + o0 <= 247; idle / outside samples
+            // take a byte pair no sample and no other group has (125 + grp)
+            const uint32_t key = (uint32_t)((r1 * 5 + q1) * 10 + o0);
+            const uint32_t kk = inside[u] ? (key >> 1) | (((key + 1) >> 1) << 8) : (uint32_t)(125 + grp) * 0x0101u;
+            keys |= kk << (16 * u);
         }
         const f2v w[2][4] = {{f2v{c000.x, c001.x}, f2v{c010.x, c011.x}, f2v{c100.x, c101.x}, f2v{c110.x, c111.x}},
                              {f2v{c000.y, c001.y}, f2v{c010.y, c011.y}, f2v{c100.y, c101.y}, f2v{c110.y, c111.y}}};
@@ -577,6 +650,29 @@ __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img
                 if (inside[u])
                     sink += (w[u][0] + w[u][1]) * (w[u][2] + w[u][3]) +
                             f2v{(float)a[u][0], (float)(a[u][1] + a[u][2] + a[u][3])};
+            continue;
+        }
+        bool rounds = true;  // the four-round form
+        if constexpr ((kShare == 2 || kShare == 4) && !(kAblate & 16))
+            rounds = __builtin_amdgcn_ballot_w64(partner_key_match<kShare>(keys)) != 0;
+        if constexpr ((kAblate & 32) != 0) {
+            probe->iters++;
+            probe->fallbacks += rounds ? 1 : 0;
+        }
+        if (!rounds) {
+            // one pass: every lane in the same instruction, corner by corner
+            // (neighbouring origins share cells across different corners)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                if (!inside[u]) continue;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const f2v sum = f2v{hp[a[u][j]], hp[a[u][j] + NS]} + w[u][j];
+                    hp[a[u][j]] = sum.x;
+                    hp[a[u][j] + NS] = sum.y;
+                    asm volatile("" ::: "memory");  // the next corner's read stays behind this write
+                }
+            }
             continue;
         }
 #pragma unroll
@@ -640,6 +736,7 @@ __device__ __forceinline__ void describe_wave_fast(const float* __restrict__ img
     }
     if ((lane & 3) == 0) acc0 += acc8;
     if (kAblate & 1) acc0 += sink.x + sink.y;
+    if constexpr ((kAblate & 32) != 0) reinterpret_cast<float2*>(probe->raw)[lane] = make_float2(acc0, acc1);
     describe_normalize<true>(acc0, acc1, out, lane);
 }
 
@@ -690,6 +787,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kMode == 0 ?
     uint32_t i = take();
     KpRec kp = record(i);
     uint32_t nsamp = 0;  // samples enumerated by this wave (sample counting)
+    DescProbe probe;     // kAblate bit 5 only
     while (i < n) {
         if (drained < kDescQueues) issue();
         const int o = __builtin_amdgcn_readfirstlane(kp.octave);
@@ -709,6 +807,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kMode == 0 ?
             ni = drained < kDescQueues ? take() : n;
             nkp = record(ni);
         };
+        if constexpr ((kAblate & 32) != 0) probe.raw = L.probe_raw + (size_t)i * kDescSize;
         if constexpr (kExact) {
             describe_wave_exact<kAblate>(img, pitch, W, H, kp.x * osf, kp.y * osf, kp_size, angle, kp.sin_d, kp.cos_d,
                                          scr, out, lane);
@@ -716,7 +815,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kMode == 0 ?
         } else {
             describe_wave_fast<kExact ? 1 : kMode, kAblate>(img, pitch, W, H, kp.x * osf, kp.y * osf, kp_size, angle,
                                                             kp.sin_d, kp.cos_d, scr, out, lane, next,
-                                                            L.samples ? &nsamp : nullptr);
+                                                            L.samples ? &nsamp : nullptr, &probe);
         }
         if (lane == 0) {
             if (L.out_kp) {
@@ -735,6 +834,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kMode == 0 ?
         kp = nkp;
     }
     if (L.samples && lane == 0 && nsamp) atomicAdd(L.samples + (blockIdx.x & 7), (unsigned long long)nsamp);
+    if constexpr ((kAblate & 32) != 0) {
+        if (lane == 0) {
+            atomicAdd(L.probe_iters, (unsigned long long)probe.iters);
+            atomicAdd(L.probe_iters + 1, (unsigned long long)probe.fallbacks);
+        }
+    }
 }
 
 void launch_describe(const DescLaunch& L, hipStream_t st) {

@@ -331,6 +331,9 @@ struct DescLaunch {
     uint8_t* out_desc;
     int exact;         // 1: bit-exact bin-owner accumulation (describe_wave_exact)
     unsigned long long* samples;  // 8 counters (measurement only; null: off)
+    // micro-benchmark probes (k_describe's kAblate bit 5 only; null in the product)
+    float* probe_raw;                 // 128 bin sums per keypoint before normalisation
+    unsigned long long* probe_iters;  // sample-loop iterations, four-round iterations
 };
 void launch_describe(const DescLaunch& L, hipStream_t st);
 

@@ -814,6 +814,11 @@ int main(int argc, char** argv) {
         k.size = 1.8f + 1.8f * (float)(rand() % 1000) / 1000.f;
         k.angle = 0.5f + (float)(rand() % 3590) / 10.f;
         k.response = 0.1f;
+        // the descriptor rotation k_orient stores with the keypoint (desc_rotation);
+        // left at 0 every sample of a window falls into one cell
+        const float rad = (360.0f - k.angle) * (3.14159265358979323846f / 180.0f);
+        k.sin_d = (float)sin((double)rad);
+        k.cos_d = (float)cos((double)rad);
     }
     float* d_img;
     KpRec* d_kp;
@@ -862,6 +867,48 @@ int main(int argc, char** argv) {
     std::printf("  fast s2         %8.3f ms\n", time_describe<2, 0>(L, reps));
     std::printf("  fast s4         %8.3f ms\n", time_describe<4, 0>(L, reps));
     std::printf("  fast s4 -rmw    %8.3f ms\n", time_describe<4, 1>(L, reps));
+    // band walk + one-pass scatter (the default above) against the four-round
+    // scatter on the same walk (kAblate bit 4); bit 5 fills the probes
+    std::printf("  fast s4 4round  %8.3f ms\n", time_describe<4, 16>(L, reps));
+    std::printf("  fast s2 4round  %8.3f ms\n", time_describe<2, 16>(L, reps));
+    {
+        std::vector<float> one((size_t)NKP * 128), four((size_t)NKP * 128);
+        unsigned long long it[2];
+        CK(hipMalloc(&L.probe_raw, one.size() * 4));
+        CK(hipMalloc(&L.probe_iters, sizeof(it)));
+        auto probe = [&](auto run, std::vector<float>& bins) {
+            CK(hipMemset(L.probe_iters, 0, sizeof(it)));
+            run();
+            CK(hipMemcpy(bins.data(), L.probe_raw, bins.size() * 4, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(it, L.probe_iters, sizeof(it), hipMemcpyDeviceToHost));
+        };
+        auto compare = [&](const char* name) {
+            // raw bin sums of the two scatter forms: reordering moves a bin by
+            // ~1e-7 relative, a lost update by ~7e-4
+            double worst = 0.0;
+            size_t bad = 0;
+            for (size_t i = 0; i < one.size(); i++) {
+                const double a = one[i], b = four[i], m = std::max(std::fabs(a), std::fabs(b));
+                const double rel = m > 0.0 ? std::fabs(a - b) / m : 0.0;
+                worst = std::max(worst, rel);
+                bad += rel > 1e-5;
+            }
+            std::printf("  %s raw bins one-pass vs 4round: max rel diff %.3g, %zu of %zu above 1e-5: %s\n", name, worst,
+                        bad, one.size(), bad ? "FAIL" : "ok");
+        };
+        probe([&] { time_describe<4, 32>(L, 0); }, one);
+        std::printf("  fast s4 fallback iterations %llu of %llu (%.3f %%)\n", it[1], it[0], 100.0 * it[1] / it[0]);
+        probe([&] { time_describe<4, 48>(L, 0); }, four);
+        compare("s4");
+        probe([&] { time_describe<2, 32>(L, 0); }, one);
+        std::printf("  fast s2 fallback iterations %llu of %llu (%.3f %%)\n", it[1], it[0], 100.0 * it[1] / it[0]);
+        probe([&] { time_describe<2, 48>(L, 0); }, four);
+        compare("s2");
+        CK(hipFree(L.probe_raw));
+        CK(hipFree(L.probe_iters));
+        L.probe_raw = nullptr;
+        L.probe_iters = nullptr;
+    }
     std::printf("  fast s4 nosample %8.3f ms\n", time_describe<4, 64>(L, reps));
     std::printf("  fast s4 f32sincos %8.3f ms\n", time_describe<4, 128>(L, reps));
     std::printf("  fast s4 nosample f32sincos %8.3f ms\n", time_describe<4, 192>(L, reps));
