@@ -1,0 +1,633 @@
+// libsift_mi.so: the C ABI of include/sift_mi.h over the pipeline
+// (pipeline.cpp) and the HIP kernels in this directory, the contexts' stream
+// pool and the stand-alone Processing ops.
+#include <cmath>
+#include <mutex>
+#include <thread>
+
+#include "host_internal.h"
+
+using namespace siftmi;
+
+namespace {
+// Process-wide pool of the contexts' streams (per device, in creation
+// order).  HIP maps streams onto a few hardware queues (GPU_MAX_HW_QUEUES,
+// 4 by default) as they are created; a context created after another was
+// destroyed would otherwise get a different, possibly colliding mapping
+// (measured: one 1080p frame per call 0.69 ms in a fresh process, 0.89 ms
+// after a closed batch context -- the octave overlap's two streams had landed
+// on one queue).  A closed context returns its streams here; the next one
+// takes the same stream objects back, so every context sees the queue
+// mapping of the first.
+struct StreamPool {
+    std::mutex mu;
+    std::vector<std::vector<hipStream_t>> free_sets[64];  // per device: sets of kCtxStreams
+};
+StreamPool& stream_pool() {
+    static StreamPool* p = new StreamPool();  // never destroyed: streams live until process exit
+    return *p;
+}
+// the order matters for the queue mapping: lane 0, lane 1, lane 0's aux,
+// the copy stream, lane 1's aux, lane 0's second aux (with 4 queues the last
+// two share the lanes' queues: lane 1's aux is used only when lane 1 is idle,
+// the second aux only while lane 1's stream is: a one-lane / one-chunk call)
+constexpr int kCtxStreams = 6;
+bool take_streams(int dev, hipStream_t (&out)[kCtxStreams]) {
+    StreamPool& P = stream_pool();
+    {
+        std::lock_guard<std::mutex> g(P.mu);
+        auto& fs = P.free_sets[dev & 63];
+        if (!fs.empty()) {
+            for (int i = 0; i < kCtxStreams; i++) out[i] = fs.back()[i];
+            fs.pop_back();
+            return true;
+        }
+    }
+    for (int i = 0; i < kCtxStreams; i++) {
+        if (hipStreamCreateWithFlags(&out[i], hipStreamNonBlocking) != hipSuccess) {
+            for (int k = 0; k < i; k++) (void)hipStreamDestroy(out[k]);
+            return false;
+        }
+    }
+    return true;
+}
+void give_streams(int dev, const hipStream_t (&in)[kCtxStreams]) {
+    StreamPool& P = stream_pool();
+    std::lock_guard<std::mutex> g(P.mu);
+    P.free_sets[dev & 63].emplace_back(in, in + kCtxStreams);
+}
+
+// The events that only order the context's streams on the device (octave
+// hand-overs, forks, joins, the one-frame path's oriented / ordered).
+// (Measured: a device-scope release, hipEventReleaseToDevice, changed nothing
+// -- 0.581-0.583 ms per 1080p frame either way; a signalling kernel still
+// costs its stream ~5 us before the next one starts)
+bool create_sync_events(sift_mi_ctx* c) {
+    auto make = [&](hipEvent_t& e) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+        return hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    };
+    bool ok = make(c->fork) && make(c->aux2_join);
+    for (auto& lane : c->oct_ev)
+        for (auto& e : lane) ok = ok && make(e);
+    for (auto& S : c->slot) ok = ok && make(S.ordered) && make(S.oriented);
+    return ok;
+}
+
+// Host copy of large results: split across threads (the copy is bound by
+// page faults on freshly allocated destinations as much as by bandwidth).
+void par_memcpy(void* dst, const void* src, size_t bytes) {
+    constexpr size_t kPerThread = 4u << 20;
+    const unsigned hw = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+    const unsigned nt = (unsigned)std::min<size_t>(hw, bytes / kPerThread);
+    if (nt <= 1) {
+        std::memcpy(dst, src, bytes);
+        return;
+    }
+    const size_t part = (bytes / nt + 4095) & ~(size_t)4095;
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) {
+        const size_t a = t * part;
+        if (a >= bytes) break;
+        const size_t b = std::min(bytes, a + part);
+        th.emplace_back([=] { std::memcpy((char*)dst + a, (const char*)src + a, b - a); });
+    }
+    std::memcpy(dst, src, std::min(bytes, part));
+    for (auto& x : th) x.join();
+}
+
+int octave_dims(const Plan& p, size_t o, uint32_t* w, uint32_t* h) {
+    if (o >= (size_t)p.n_oct) return fail(SIFT_MI_EINVAL, "octave out of range");
+    if (w) *w = (uint32_t)p.ow[o];
+    if (h) *h = (uint32_t)p.oh[o];
+    return 0;
+}
+
+// n consecutive pitched planes of octave o at src to the dense host array out
+int read_planes(const Plan& p, int o, const float* src, int n, float* out) {
+    HIPCHK(hipMemcpy2D(out, (size_t)p.ow[o] * sizeof(float), src, (size_t)p.opitch[o] * sizeof(float),
+                       (size_t)p.ow[o] * sizeof(float), (size_t)n * p.oh[o], hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// image::imageops::resize on a host f32 image (Imageproc profile ops).
+int ip_resize_op(sift_mi_ctx* c, const float* src, uint32_t w, uint32_t h, uint32_t dw, uint32_t dh, float support,
+                 float* dst) {
+    if (w == dw && h == dh) {  // image's resize copies when the size is unchanged
+        std::memcpy(dst, src, sizeof(float) * (size_t)w * h);
+        return 0;
+    }
+    IpTabDev tab;
+    CHK(tab.upload((int)w, (int)h, (int)dw, (int)dh, support, 1, c->stream));
+    DevBuf<float> a, t, b;
+    CHK(upload(a, src, (size_t)w * h, c->stream));
+    CHK(t.ensure((size_t)w * dh));
+    CHK(b.ensure((size_t)dw * dh));
+    launch_ip_resize_f32(a.p, (int)w, (int)h, tab.xl.p, tab.xw.p, tab.xtaps, tab.yl.p, tab.yw.p, tab.ytaps, t.p, b.p,
+                         (int)dw, (int)dh, c->stream);
+    return download(dst, b, (size_t)dw * dh, c->stream);
+}
+}  // namespace
+
+extern "C" {
+
+const char* sift_mi_version(void) { return "sift_mi 0.4.0 (gfx950)"; }
+const char* sift_mi_last_error(void) { return g_err.c_str(); }
+
+int sift_mi_create(int device_ordinal, sift_mi_profile profile, sift_mi_ctx** out) {
+    if (!out) return fail(SIFT_MI_EINVAL, "out is null");
+    *out = nullptr;
+    if (profile != SIFT_MI_PROFILE_OPENCV && profile != SIFT_MI_PROFILE_IMAGEPROC)
+        return fail(SIFT_MI_EINVAL, "unknown profile");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SIFT_MI_ENODEV, "no HIP device");
+    if (device_ordinal < 0 || device_ordinal >= ndev) return fail(SIFT_MI_ENODEV, "device ordinal out of range");
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device_ordinal));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(SIFT_MI_ENODEV, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950");
+    HIPCHK(hipSetDevice(device_ordinal));
+    sift_mi_ctx* c = new sift_mi_ctx();
+    c->device = device_ordinal;
+    c->profile = profile;
+    hipStream_t ss[kCtxStreams];
+    if (!take_streams(device_ordinal, ss)) {
+        delete c;
+        return fail(SIFT_MI_EHIP, "hipStreamCreate failed");
+    }
+    c->own = ss[0];
+    c->own2 = ss[1];
+    c->aux[0] = ss[2];
+    c->cstream = ss[3];
+    c->aux[1] = ss[4];
+    c->aux2 = ss[5];
+    c->stream = c->own;
+    bool ok = create_sync_events(c);
+    for (auto& S : c->slot) {
+        for (auto& e : S.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&S.copied, hipEventDisableTiming) == hipSuccess;
+    }
+    if (!ok) {
+        sift_mi_destroy(c);
+        return fail(SIFT_MI_EHIP, "stream / event creation failed");
+    }
+    *out = c;
+    return 0;
+}
+
+void sift_mi_destroy(sift_mi_ctx* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    // every stream that may still run work on this context's buffers first:
+    // the caller's stream (sift_mi_set_stream), the context's own lane-0
+    // stream (it goes back to the pool below), lane 1, both aux streams
+    // (octave blurs 4, 5 and detection write the arenas) and the copy stream
+    {
+        const hipStream_t ss[] = {c->stream, c->own, c->own2, c->aux[0], c->aux[1], c->aux2, c->cstream, c->dec};
+        for (hipStream_t s : ss)
+            if (s) (void)hipStreamSynchronize(s);
+    }
+    auto destroy = [](hipEvent_t e) {
+        if (e) (void)hipEventDestroy(e);
+    };
+    for (auto& S : c->slot) {
+        for (auto& e : S.ev) destroy(e);
+        destroy(S.copied);
+        destroy(S.ordered);
+        destroy(S.oriented);
+    }
+    destroy(c->fork);
+    destroy(c->aux2_join);
+    for (auto& lane : c->oct_ev)
+        for (auto& e : lane) destroy(e);
+    c->jpeg.release();  // (its events too)
+    if (c->dec) (void)hipStreamDestroy(c->dec);
+    if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
+    if (c->graph) (void)hipGraphDestroy(c->graph);
+    if (c->own) {  // the streams go back to the pool (synchronised above)
+        const hipStream_t ss[kCtxStreams] = {c->own, c->own2, c->aux[0], c->cstream, c->aux[1], c->aux2};
+        give_streams(c->device, ss);
+    }
+    delete c;  // frees every buffer the context, its plan and its slots own
+}
+
+int sift_mi_set_stream(sift_mi_ctx* c, void* s) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    c->stream = s ? (hipStream_t)s : c->own;
+    return 0;
+}
+
+int sift_mi_set_chunk(sift_mi_ctx* c, uint32_t k) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    c->chunk_override = k;
+    return 0;
+}
+
+int sift_mi_set_max_octaves(sift_mi_ctx* c, int max_octaves) {
+    if (!c || max_octaves < 0) return fail(SIFT_MI_EINVAL, "max_octaves must be >= 0");
+    CHK(set_device(c));
+    CHK(sync_lanes(c));
+    c->max_octaves = max_octaves;  // the plan is rebuilt on the next call
+    c->have_pyramid = false;
+    return 0;
+}
+
+int sift_mi_set_exact_descriptors(sift_mi_ctx* c, int exact) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    c->exact_descriptors = exact ? 1 : 0;
+    return 0;
+}
+
+int sift_mi_set_pipeline_lanes(sift_mi_ctx* c, int lanes) {
+    if (!c || (lanes != 1 && lanes != 2)) return fail(SIFT_MI_EINVAL, "lanes must be 1 or 2");
+    CHK(set_device(c));
+    CHK(sync_lanes(c));
+    c->lanes = lanes;
+    return 0;
+}
+
+int sift_mi_set_row_band(sift_mi_ctx* c, uint32_t band, uint32_t n_bands) {
+    if (!c || n_bands == 0 || band >= n_bands) return fail(SIFT_MI_EINVAL, "band must be < n_bands, n_bands >= 1");
+    c->band_r = band;
+    c->band_n = n_bands;
+    return 0;
+}
+
+int sift_mi_set_path_option(sift_mi_ctx* c, int option, int value) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    CHK(set_device(c));
+    CHK(sync_lanes(c));  // no chunk in flight sees a half-changed path
+    PathOpts& o = c->opts;
+    const bool b = value == 0 || value == 1;
+    switch (option) {
+        case SIFT_MI_PATH_TILE_BLUR: if (!b) break; o.tile_blur = value; return 0;
+        case SIFT_MI_PATH_PAIR_BLUR: if (!b) break; o.pair = value; return 0;
+        case SIFT_MI_PATH_SEED_PAIR: if (!b) break; o.seed_pair = value; return 0;
+        case SIFT_MI_PATH_TAIL: if (!b) break; o.tail = value; return 0;
+        case SIFT_MI_PATH_FUSED_DETECT: if (value < 0 || value > 2) break; o.fused_detect = value; return 0;
+        case SIFT_MI_PATH_EARLY: if (!b) break; o.early = value; return 0;
+        case SIFT_MI_PATH_DESC_FIRST: if (!b) break; o.desc_first = value; return 0;
+        case SIFT_MI_PATH_GRAPH: if (!b) break; o.graph = value; return 0;
+        case SIFT_MI_PATH_BAND_DRIFT: if (value < -kBandPatch || value > kBandDrift) break; o.band_drift = value; return 0;
+        case SIFT_MI_PATH_BOUND_SHRINK: if (value < 1) break; o.bound_shrink = value; return 0;
+        case SIFT_MI_PATH_LARGE_FIRST: if (!b) break; o.large_first = value; return 0;
+        case SIFT_MI_PATH_ONESWEEP: if (value < 0 || value > 2) break; o.onesweep = value; return 0;
+        case SIFT_MI_PATH_BD_PAIR: if (value < 0 || value > 2) break; o.bd_pair = value; return 0;
+        case SIFT_MI_PATH_BD_WAVES: if (value < 1024 || value > 65536) break; o.bd_waves = value; return 0;
+        case SIFT_MI_PATH_CHUNK_MODE: if (value < 0 || value > 1) break; o.chunk_mode = value; return 0;
+        default: return fail(SIFT_MI_EINVAL, "unknown path option");
+    }
+    return fail(SIFT_MI_EINVAL, "path option value out of range");
+}
+
+int sift_mi_set_keep_on_device(sift_mi_ctx* c, int keep) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    c->keep_on_device = keep ? 1 : 0;
+    return 0;
+}
+
+int sift_mi_extract_batch_device(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, uint32_t n,
+                                 uint32_t w, uint32_t h, size_t stride, int64_t limit, size_t* offsets) {
+    if (!c || !d_frames || n == 0) return fail(SIFT_MI_EINVAL, "bad arguments");
+    if (frame_pitch < stride * (h - 1) + w && n > 1) return fail(SIFT_MI_EINVAL, "frame_pitch too small");
+    CHK(set_device(c));
+    return extract_device(c, d_frames, frame_pitch, n, w, h, stride, limit, offsets);
+}
+
+int sift_mi_extract_batch(sift_mi_ctx* c, const uint8_t* const* frames, uint32_t n, uint32_t w, uint32_t h,
+                          size_t stride, int64_t limit, size_t* offsets) {
+    if (!c || !frames || n == 0) return fail(SIFT_MI_EINVAL, "bad arguments");
+    CHK(check_frame_args(w, h, stride));
+    CHK(set_device(c));
+    CHK(upload_frames(c, frames, n, w, h, stride));
+    const int keep = c->keep_on_device;
+    c->keep_on_device = 0;
+    const int rc = extract_device(c, c->staging.p, (size_t)w * h, n, w, h, w, limit, offsets);
+    c->keep_on_device = keep;
+    return rc;
+}
+
+int sift_mi_extract(sift_mi_ctx* c, const uint8_t* pixels, uint32_t w, uint32_t h, size_t stride, int64_t limit,
+                    size_t* n_keypoints) {
+    if (!c || !pixels) return fail(SIFT_MI_EINVAL, "bad arguments");
+    const uint8_t* frames[1] = {pixels};
+    size_t offs[2];
+    CHK(sift_mi_extract_batch(c, frames, 1, w, h, stride, limit, offs));
+    if (n_keypoints) *n_keypoints = offs[1];
+    return 0;
+}
+
+int sift_mi_fetch(sift_mi_ctx* c, sift_mi_keypoint* kps, uint8_t* desc, size_t cap) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    if (!c->have_result || c->keep_on_device) return fail(SIFT_MI_ESTATE, "no host result to fetch");
+    if (cap < c->n_result) return fail(SIFT_MI_EINVAL, "cap < result size");
+    static_assert(sizeof(sift_mi_keypoint) == sizeof(OutKp), "layout");
+    if (kps && c->n_result) par_memcpy(kps, c->h_kp.p, c->n_result * sizeof(OutKp));
+    if (desc && c->n_result) par_memcpy(desc, c->h_desc.p, c->n_result * kDescSize);
+    return 0;
+}
+
+int sift_mi_fetch_keys(sift_mi_ctx* c, uint64_t* keys, size_t cap) {
+    if (!c || !keys) return fail(SIFT_MI_EINVAL, "bad arguments");
+    if (!c->have_result || c->keep_on_device) return fail(SIFT_MI_ESTATE, "no host result to fetch");
+    if (cap < c->n_result) return fail(SIFT_MI_EINVAL, "cap < result size");
+    if (c->n_result) par_memcpy(keys, c->h_key.p, c->n_result * sizeof(uint64_t));
+    return 0;
+}
+
+int sift_mi_device_results(sift_mi_ctx* c, const sift_mi_keypoint** d_kps, const uint8_t** d_desc, size_t* n) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    if (!c->have_result) return fail(SIFT_MI_ESTATE, "no result");
+    if (!c->keep_on_device) return fail(SIFT_MI_ESTATE, "results were copied to the host (keep_on_device is 0)");
+    const bool direct = c->res_slot >= 0;
+    const Slot& S = c->slot[direct ? c->res_slot : 0];
+    if (d_kps) *d_kps = reinterpret_cast<const sift_mi_keypoint*>(direct ? S.out_kp.p : c->r_kp.p);
+    if (d_desc) *d_desc = direct ? S.out_desc.p : c->r_desc.p;
+    if (n) *n = c->n_result;
+    return 0;
+}
+
+// ---- precompute_images / sift_with_precomputed (single frame) -------------
+int sift_mi_precompute(sift_mi_ctx* c, const uint8_t* pixels, uint32_t w, uint32_t h, size_t stride,
+                       size_t* n_octaves) {
+    if (!c || !pixels) return fail(SIFT_MI_EINVAL, "bad arguments");
+    CHK(check_frame_args(w, h, stride));
+    CHK(set_device(c));
+    const uint8_t* frames[1] = {pixels};
+    c->batch_arena = -1;  // arena 0 is rewritten: the last batch's planes are gone
+    CHK(upload_frames(c, frames, 1, w, h, stride));
+    CHK(ensure_plan(c, w, h, 1));
+    CHK(run_pyramid(c, 0, c->staging.p, (size_t)w * h, w, 1, true));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->have_pyramid = true;
+    c->have_result = false;
+    if (n_octaves) *n_octaves = (size_t)c->plan.n_oct;
+    return 0;
+}
+
+int sift_mi_octave_dims(sift_mi_ctx* c, size_t o, uint32_t* w, uint32_t* h) {
+    if (!c || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    return octave_dims(c->plan, o, w, h);
+}
+
+int sift_mi_read_scale_space(sift_mi_ctx* c, size_t o, float* out) {
+    if (!c || !out || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    if (o >= (size_t)c->plan.n_oct) return fail(SIFT_MI_EINVAL, "octave out of range");
+    CHK(set_device(c));
+    return read_planes(c->plan, (int)o, c->plan.gauss((int)o), kImagesPerOctave, out);
+}
+
+int sift_mi_batch_octave_dims(sift_mi_ctx* c, size_t o, uint32_t* w, uint32_t* h) {
+    if (!c || c->batch_arena < 0) return fail(SIFT_MI_ESTATE, "no single-chunk batch pyramid");
+    return octave_dims(c->plan, o, w, h);
+}
+
+int sift_mi_read_batch_scale_space(sift_mi_ctx* c, uint32_t frame, size_t o, float* out, size_t out_floats) {
+    if (!c || !out || c->batch_arena < 0) return fail(SIFT_MI_ESTATE, "no single-chunk batch pyramid");
+    Plan& p = c->plan;
+    if (o >= (size_t)p.n_oct || frame >= c->batch_frames || frame >= p.chunk)
+        return fail(SIFT_MI_EINVAL, "frame / octave out of range");
+    if (out_floats < (size_t)kImagesPerOctave * p.ow[o] * p.oh[o])
+        return fail(SIFT_MI_EINVAL, "out_floats < 6 * width * height of the octave (sift_mi_batch_octave_dims)");
+    CHK(set_device(c));
+    CHK(sync_lanes(c));
+    const float* g = p.gauss((int)o, c->batch_arena) + (size_t)frame * p.gstride((int)o);
+    return read_planes(p, (int)o, g, kImagesPerOctave, out);
+}
+
+int sift_mi_read_dog(sift_mi_ctx* c, size_t o, float* out) {
+    if (!c || !out || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    if (o >= (size_t)c->plan.n_oct) return fail(SIFT_MI_EINVAL, "octave out of range");
+    CHK(set_device(c));
+    return read_planes(c->plan, (int)o, c->plan.dog((int)o), kDogPerOctave, out);
+}
+
+int sift_mi_sift_with_precomputed(sift_mi_ctx* c, int64_t limit, size_t* n_keypoints) {
+    if (!c || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    CHK(set_device(c));
+    c->batch_arena = -1;  // a later call: the batch read-back is no longer valid
+    const int keep = c->keep_on_device;
+    c->keep_on_device = 0;
+    size_t offs[2];
+    const int rc = run_chunk_sync(c, nullptr, 0, 0, 1, limit, false, offs);
+    c->keep_on_device = keep;
+    CHK(rc);
+    c->have_result = true;
+    if (n_keypoints) *n_keypoints = offs[1];
+    return 0;
+}
+
+// ---- compute_descriptor --------------------------------------------------
+int sift_mi_compute_descriptor(sift_mi_ctx* c, const float* img, uint32_t w, uint32_t h, float x, float y,
+                               float scale, float orientation, uint8_t* out) {
+    if (!c || !img || !out || w < 1 || h < 1) return fail(SIFT_MI_EINVAL, "bad arguments");
+    // window radius round(10.61 * scale) <= 39 (the device scratch); the
+    // pipeline's keypoints have scale < 3.6 (radius <= 38)
+    if (!(scale > 0.f) || roundf(3.0f * scale * 1.41421356f * 5.0f * 0.5f) > 39.0f)
+        return fail(SIFT_MI_EUNSUPPORTED, "scale outside (0, 3.7]: descriptor window radius > 39");
+    // the reference indexes its histogram out of bounds (panics) outside [0, 360]
+    if (!(orientation >= 0.f && orientation <= 360.f)) return fail(SIFT_MI_EINVAL, "orientation outside [0, 360]");
+    CHK(set_device(c));
+    DevBuf<float> dimg;
+    DevBuf<uint8_t> dout;
+    CHK(upload(dimg, img, (size_t)w * h, c->stream));
+    CHK(dout.ensure(kDescSize));
+    launch_describe_one(dimg.p, (int)w, (int)h, x, y, scale, orientation, dout.p, c->stream);
+    return download(out, dout, kDescSize, c->stream);
+}
+
+// ---- Processing ops ------------------------------------------------------
+int sift_mi_gaussian_blur(sift_mi_ctx* c, const float* src, uint32_t w, uint32_t h, double sigma, float* dst) {
+    if (!c || !src || !dst || w < 2 || h < 2 || !(sigma > 0)) return fail(SIFT_MI_EINVAL, "bad arguments");
+    CHK(set_device(c));
+    BlurTaps taps;
+    const bool ip = c->profile == SIFT_MI_PROFILE_IMAGEPROC;
+    const int r = ip ? ip_blur_taps((float)sigma, &taps) : cv_blur_taps(sigma, &taps);
+    if (r < 1) return fail(SIFT_MI_EUNSUPPORTED, "blur radius outside 1..24");
+    DevBuf<float> a, b;
+    const size_t pitch = ((size_t)w + 63) & ~(size_t)63;  // same row alignment as the pyramid
+    CHK(a.ensure(pitch * h));
+    CHK(b.ensure(pitch * h));
+    BlurLaunch L{};
+    L.src = a.p;
+    L.dst = b.p;
+    L.W = (int)w;
+    L.H = (int)h;
+    L.pitch = (int)pitch;
+    L.n_img = 1;
+    L.taps = taps;
+    L.profile = ip ? kProfileImageproc : kProfileOpenCV;
+    if (hipMemcpy2DAsync(a.p, pitch * 4, src, (size_t)w * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, c->stream) !=
+            hipSuccess ||
+        launch_blur(r, L, c->stream, c->opts) != 0 ||
+        hipMemcpy2DAsync(dst, (size_t)w * 4, b.p, pitch * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost, c->stream) !=
+            hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(SIFT_MI_EHIP, "gaussian_blur failed");
+    return 0;
+}
+
+int sift_mi_resize_linear(sift_mi_ctx* c, const float* src, uint32_t w, uint32_t h, uint32_t dw, uint32_t dh,
+                          float* dst) {
+    if (!c || !src || !dst || !w || !h || !dw || !dh) return fail(SIFT_MI_EINVAL, "bad arguments");
+    CHK(set_device(c));
+    if (c->profile == SIFT_MI_PROFILE_IMAGEPROC) return ip_resize_op(c, src, w, h, dw, dh, 1.0f, dst);
+    ResizeTabDev tab;
+    CHK(tab.upload((int)w, (int)h, (int)dw, (int)dh, c->stream));
+    DevBuf<float> a, b;
+    CHK(upload(a, src, (size_t)w * h, c->stream));
+    CHK(b.ensure((size_t)dw * dh));
+    launch_resize_linear_f32(a.p, (int)w, (int)h, tab.tab, b.p, (int)dw, (int)dh, c->stream);
+    return download(dst, b, (size_t)dw * dh, c->stream);
+}
+
+int sift_mi_resize_nearest(sift_mi_ctx* c, const float* src, uint32_t w, uint32_t h, uint32_t dw, uint32_t dh,
+                           float* dst) {
+    if (!c || !src || !dst || !w || !h || !dw || !dh) return fail(SIFT_MI_EINVAL, "bad arguments");
+    CHK(set_device(c));
+    if (c->profile == SIFT_MI_PROFILE_IMAGEPROC) return ip_resize_op(c, src, w, h, dw, dh, 0.0f, dst);
+    std::vector<int> xo, yo;
+    cv_nearest_ofs((int)w, (int)dw, xo);
+    cv_nearest_ofs((int)h, (int)dh, yo);
+    DevBuf<float> a, b;
+    DevBuf<int> dx, dy;
+    CHK(upload(a, src, (size_t)w * h, c->stream));
+    CHK(upload(dx, xo.data(), dw, c->stream));
+    CHK(upload(dy, yo.data(), dh, c->stream));
+    CHK(b.ensure((size_t)dw * dh));
+    launch_resize_nearest_f32(a.p, (int)w, dx.p, dy.p, b.p, (int)dw, (int)dh, c->stream);
+    return download(dst, b, (size_t)dw * dh, c->stream);
+}
+
+// ---- descriptor matching (examples/sift-match.rs:30-35) ---------------------
+int sift_mi_match_descriptors(sift_mi_ctx* c, const uint8_t* query, size_t nq, const uint8_t* train, size_t nt,
+                              int cross_check, sift_mi_match* out, size_t cap, size_t* n_matches) {
+    if (!c || !n_matches || (nq && !query) || (nt && !train)) return fail(SIFT_MI_EINVAL, "bad arguments");
+    if (nq > 0x7fffffff || nt > 0x7fffffff) return fail(SIFT_MI_EINVAL, "descriptor set too large");
+    *n_matches = 0;
+    if (nq == 0) return 0;
+    CHK(set_device(c));
+    DevBuf<uint8_t> dq, dt;
+    DevBuf<float> qn, tn, dist;
+    DevBuf<unsigned long long> rb, cb;
+    DevBuf<int> tix;
+    hipStream_t st = c->stream;
+    CHK(upload(dq, query, nq * kDescSize, st));
+    CHK(dt.ensure(std::max<size_t>(nt, 1) * kDescSize));
+    if (nt) CHK(upload(dt, train, nt * kDescSize, st));
+    CHK(qn.ensure(nq));
+    CHK(tn.ensure(std::max<size_t>(nt, 1)));
+    CHK(rb.ensure(nq));
+    CHK(cb.ensure(std::max<size_t>(nt, 1)));
+    CHK(tix.ensure(nq));
+    CHK(dist.ensure(nq));
+    std::vector<int> h_t(nq);
+    std::vector<float> h_d(nq);
+    launch_match(dq.p, (int)nq, dt.p, (int)nt, cross_check ? 1 : 0, qn.p, tn.p, rb.p, cb.p, tix.p, dist.p, st);
+    HIPCHK(hipGetLastError());
+    CHK(download(h_t.data(), tix, nq, st));
+    CHK(download(h_d.data(), dist, nq, st));
+    size_t n = 0;
+    for (size_t i = 0; i < nq; i++) n += h_t[i] >= 0;
+    *n_matches = n;
+    if (cap < n || (n && !out)) return fail(SIFT_MI_EINVAL, "cap < number of matches");
+    size_t k = 0;
+    for (size_t i = 0; i < nq; i++)
+        if (h_t[i] >= 0) out[k++] = sift_mi_match{(int32_t)i, h_t[i], h_d[i]};
+    return 0;
+}
+
+int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height) {
+    if (!data || !width || !height) return fail(SIFT_MI_EINVAL, "bad arguments");
+    std::string err;
+    const int rc = jpeg_dims(data, len, width, height, err);
+    return rc ? fail(rc, err) : 0;
+}
+
+int sift_mi_decode_jpeg(sift_mi_ctx* c, const uint8_t* data, size_t len, uint8_t* out, size_t out_stride,
+                        int out_on_device) {
+    if (!c || !data || !out) return fail(SIFT_MI_EINVAL, "bad arguments");
+    uint32_t w = 0, h = 0;
+    std::string err;
+    int rc = jpeg_dims(data, len, &w, &h, err);
+    if (rc) return fail(rc, err);
+    if (out_stride < w) return fail(SIFT_MI_EINVAL, "out_stride < width");
+    CHK(set_device(c));
+    rc = jpeg_decode_luma(data, len, out, out_stride, out_on_device != 0, c->stream, err);
+    return rc ? fail(rc, err) : 0;
+}
+
+int sift_mi_decode_jpeg_batch(sift_mi_ctx* c, const uint8_t* const* data, const size_t* len, uint32_t n,
+                              uint8_t* d_frames, size_t frame_pitch, size_t row_stride, int threads) {
+    if (!c || (n && (!data || !len || !d_frames))) return fail(SIFT_MI_EINVAL, "bad arguments");
+    for (uint32_t i = 0; i < n; i++)
+        if (!data[i]) return fail(SIFT_MI_EINVAL, "null JPEG");
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    CHK(set_device(c));
+    std::string err;
+    // The reconstruction kernels run on a high-priority stream of their own
+    // (ordered after the context's stream): the runtime takes its hardware
+    // queue from the high-priority pool, so a decode pipelined beside another
+    // context's batch (bench.py configs.jpeg_e2e) does not queue behind that
+    // batch's kernels on a shared in-order queue -- normal-priority streams
+    // share GPU_MAX_HW_QUEUES (4) queues round robin.  A caller stream
+    // (sift_mi_set_stream) is used as is.  Measured (round 4), with the
+    // polling host wait (host_wait_event): 2337 -> 3063 frames/s JPEG ->
+    // keypoints, pipelined beside sift().
+    hipStream_t st = c->stream;
+    if (c->stream == c->own) {
+        if (!c->dec) {
+            int least = 0, greatest = 0;
+            HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIPCHK(hipStreamCreateWithPriority(&c->dec, hipStreamNonBlocking, greatest));
+        }
+        HIPCHK(hipEventRecord(c->fork, c->stream));
+        HIPCHK(hipStreamWaitEvent(c->dec, c->fork, 0));
+        st = c->dec;
+    }
+    const int rc = jpeg_decode_batch(data, len, n, d_frames, frame_pitch, row_stride, threads, st, c->jpeg, err);
+    return rc ? fail(rc, err) : 0;
+}
+
+int sift_mi_get_stats(sift_mi_ctx* c, sift_mi_stats* out) {
+    if (!c || !out) return fail(SIFT_MI_EINVAL, "bad arguments");
+    *out = c->stats;
+    if (c->count_samples && c->samples.p) {
+        CHK(set_device(c));
+        CHK(sync_lanes(c));
+        unsigned long long h[16];
+        HIPCHK(hipMemcpy(h, c->samples.p, sizeof h, hipMemcpyDeviceToHost));
+        out->orient_samples = out->desc_samples = 0;
+        for (int i = 0; i < 8; i++) {
+            out->orient_samples += h[i];
+            out->desc_samples += h[8 + i];
+        }
+    }
+    return 0;
+}
+
+int sift_mi_reset_stats(sift_mi_ctx* c) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    c->stats = sift_mi_stats{};
+    if (c->samples.p) {
+        CHK(set_device(c));
+        CHK(sync_lanes(c));
+        HIPCHK(hipMemset(c->samples.p, 0, 16 * sizeof(unsigned long long)));
+    }
+    return 0;
+}
+
+int sift_mi_set_sample_counting(sift_mi_ctx* c, int on) {
+    if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
+    CHK(set_device(c));
+    CHK(sync_lanes(c));
+    if (on && !c->samples.p) {
+        CHK(c->samples.ensure(16));
+        HIPCHK(hipMemset(c->samples.p, 0, 16 * sizeof(unsigned long long)));
+    }
+    c->count_samples = on ? 1 : 0;
+    return 0;
+}
+
+}  // extern "C"

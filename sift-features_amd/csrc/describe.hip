@@ -791,10 +791,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kMode == 0 ?
     while (i < n) {
         if (drained < kDescQueues) issue();
         const int o = __builtin_amdgcn_readfirstlane(kp.octave);
-        const int W = L.ow[o], H = L.oh[o];
-        const int pitch = L.opitch[o];
-        const float* img = L.gauss[o] + (size_t)(__builtin_amdgcn_readfirstlane(kp.img) - L.img_base) *
-                                            L.gauss_img_stride[o] +
+        const int W = L.oct.ow[o], H = L.oct.oh[o];
+        const int pitch = L.oct.opitch[o];
+        const float* img = L.oct.gauss[o] + (size_t)(__builtin_amdgcn_readfirstlane(kp.img) - L.img_base) *
+                                                L.oct.img_stride[o] +
                            (size_t)__builtin_amdgcn_readfirstlane(kp.scale) * pitch * H;
         // compute_descriptors (src/lib.rs:759-782)
         const float angle = 360.0f - kp.angle;  // orientation (src/lib.rs:771); kp.sin_d / cos_d its rotation

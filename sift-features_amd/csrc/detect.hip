@@ -118,7 +118,7 @@ __device__ __forceinline__ int refine_step(const RefineLaunch& L, RefineState& s
     const gfloat* g0 = st.g0;
     const size_t P = (size_t)pitch * H;
     const int x = st.xi, y = st.yi, scale = st.sc;
-    // row bands with a restricted pyramid (host.cpp run_pyramid): the rows
+    // row bands with a restricted pyramid (pipeline.cpp PyramidRun, geometry.cpp band_rows): the rows
     // read here must be computed ones, else the host recomputes the band on
     // the whole-frame pyramid
     if (L.band_flag && (y - 1 < vlo || y + 1 >= vhi)) atomicOr(L.band_flag, 1u);
@@ -213,8 +213,8 @@ __device__ __forceinline__ int refine_step(const RefineLaunch& L, RefineState& s
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_REFINE_WPE))) void k_refine(const RefineLaunch L) {
     __shared__ RefineOct geo[16];
     if ((int)threadIdx.x < L.n_oct && threadIdx.x < 16)
-        geo[threadIdx.x] = RefineOct{L.gauss[threadIdx.x], L.g_img_stride[threadIdx.x], L.ow[threadIdx.x],
-                                     L.oh[threadIdx.x], L.opitch[threadIdx.x]};
+        geo[threadIdx.x] = RefineOct{L.oct.gauss[threadIdx.x], L.oct.img_stride[threadIdx.x], L.oct.ow[threadIdx.x],
+                                     L.oct.oh[threadIdx.x], L.oct.opitch[threadIdx.x]};
     __syncthreads();
     const uint32_t n = min(*L.n_cand, L.cand_cap);
     const int lane = threadIdx.x & 63;
@@ -313,10 +313,10 @@ __global__ __launch_bounds__(256, SIFT_ORIENT_MIN_WAVES) void k_orient(const Ori
         float acc = 0.0f;  // lane k < 36: raw_hist[k + 2]
         if (active) {
             e = L.ext[r < n_lo ? r : L.ext_cap - 1 - (r - n_lo)];
-            W = L.ow[e.octave];
-            H = L.oh[e.octave];
-            pitch = L.opitch[e.octave];
-            const float* img = L.gauss[e.octave] + (size_t)(e.img - L.img_base) * L.gauss_img_stride[e.octave] +
+            W = L.oct.ow[e.octave];
+            H = L.oct.oh[e.octave];
+            pitch = L.oct.opitch[e.octave];
+            const float* img = L.oct.gauss[e.octave] + (size_t)(e.img - L.img_base) * L.oct.img_stride[e.octave] +
                                (size_t)e.scale * pitch * H;
             osf = (float)(1u << e.octave);  // 2_f32.powi(octave)
             kp_scale = 0.8f * pow2_f32(((float)e.scale + e.off_s) / (float)kScalesPerOctave) * 2.f;
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(256, SIFT_ORIENT_MIN_WAVES) void k_orient(const Ori
 void launch_orient(const OrientLaunch& L, hipStream_t st) {
     if (L.ext_cap == 0) return;
     dim3 grid((L.ext_cap + 3) / 4);
-    klaunch(k_orient, grid, dim3(256), st, L);  // may carry a completion event (set_launch_done_event)
+    klaunch(k_orient, grid, dim3(256), st, L);  // may carry a completion event (LaunchDoneEvent)
 }
 
 }  // namespace siftmi

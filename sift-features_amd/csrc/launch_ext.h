@@ -1,8 +1,8 @@
 // Kernel launch with an optional completion event (shared by the stage
-// launchers).  The next kernel a launcher enqueues from this host thread
-// after set_launch_done_event(e) signals e on completion -- hipExtLaunchKernel's
-// stop event, no marker packet of its own: a marker between two kernels costs
-// ~7 us of the stream's timeline.
+// launchers).  While a LaunchDoneEvent is in scope, the next kernel a launcher
+// enqueues from this host thread signals its event on completion --
+// hipExtLaunchKernel's stop event, no marker packet of its own: a marker
+// between two kernels costs ~7 us of the stream's timeline.
 #pragma once
 #include <hip/hip_ext.h>
 
@@ -11,6 +11,21 @@
 namespace siftmi {
 
 inline thread_local hipEvent_t t_done = nullptr;
+
+// Arms e (null: off) for the next klaunch of this thread; taken() tells
+// whether a launch carried it (if not, the caller records e itself); leaving
+// the scope disarms it, so no later, unrelated launch can pick it up.
+class LaunchDoneEvent {
+public:
+    explicit LaunchDoneEvent(hipEvent_t e) : armed_(e != nullptr) { t_done = e; }
+    ~LaunchDoneEvent() { t_done = nullptr; }
+    LaunchDoneEvent(const LaunchDoneEvent&) = delete;
+    LaunchDoneEvent& operator=(const LaunchDoneEvent&) = delete;
+    bool taken() const { return armed_ && t_done == nullptr; }
+
+private:
+    bool armed_;
+};
 
 template <class F, class... A>
 inline void klaunch(F kernel, dim3 grid, dim3 block, hipStream_t st, A... args) {

@@ -19,9 +19,8 @@
 //                 tile + halo with 16-B global loads into LDS (reflect-101
 //                 scalar path only on border tiles), the row pass is register-
 //                 blocked (4 outputs/thread, ds_read_b128), the column pass 8
-//                 outputs/thread; the epilogue writes G_s, D_{s-1} = G_s -
-//                 G_{s-1} and, for s == 3, the next octave's base image
-//                 (nearest 1/2 = pixel (2x, 2y)).
+//                 outputs/thread; the epilogue writes G_s and, for s == 3,
+//                 the next octave's base image (nearest 1/2 = pixel (2x, 2y)).
 // The stage is HBM-bound: per octave pixel the reference materialises 6 G + 5 D
 // images (44 B); see DESIGN.md for the roofline accounting.
 #include "launch_ext.h"
@@ -33,10 +32,6 @@
 #include <cstring>
 
 namespace siftmi {
-
-void set_launch_done_event(hipEvent_t e) { t_done = e; }
-bool launch_done_pending() { return t_done != nullptr; }
-
 
 // ---------------------------------------------------------------------------
 // Tile geometry.  Input window columns [x0 - HWL, x0 + TW + HWL) with
@@ -66,8 +61,6 @@ struct BlurGeom {
 // `tin`): every row is filtered by 8 lanes of one wave, which read the whole
 // row window into registers before any of them stores (LDS executes a wave's
 // instructions in order), so no lane overwrites a value another still needs.
-// The DoG needs G_{s-1} at the tile centre: each thread copies its centre
-// values to registers before the row pass.
 // Both passes use packed f32 arithmetic (v_pk_fma_f32 / v_pk_add_f32: two
 // independent, individually rounded lanes -- the same results as scalar fma /
 // add): the row pass pairs adjacent outputs of a row, the column pass
@@ -86,19 +79,12 @@ typedef __attribute__((address_space(3))) volatile f2v lds_f2v;
 template <int R, int TH, int P = kProfileOpenCV>
 __device__ __forceinline__ void blur_tile_compute(const float* __restrict__ tin, float* __restrict__ th,
                                                   const BlurTaps& taps, int x0, int y0, int W, int H, int pitch,
-                                                  float* __restrict__ dst, float* __restrict__ dog,
-                                                  float* __restrict__ nxt, int pitch_n, int wn, int hn) {
+                                                  float* __restrict__ dst, float* __restrict__ nxt, int pitch_n,
+                                                  int wn, int hn) {
     using G = BlurGeom<R, TH>;
     constexpr int VB2 = TH / 8;  // column pass: thread = (column pair, VB2 consecutive rows)
     const int tid = threadIdx.x;
     const int cp = tid & 31, band = tid >> 5;
-    f2v centre[VB2];
-    if (dog) {
-#pragma unroll
-        for (int o = 0; o < VB2; o++)
-            centre[o] = *reinterpret_cast<const f2v*>(tin + (band * VB2 + o + R) * G::IWP + G::HWL + 2 * cp);
-        __syncthreads();  // other waves overwrite these rows in place below
-    }
     // row pass: item = (row, QW consecutive outputs); fma chain from the leftmost tap.
     // A wave filters 8 whole rows per iteration.  Lane -> (row, item) follows
     // the ds_read_b128 lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31} per
@@ -187,10 +173,8 @@ __device__ __forceinline__ void blur_tile_compute(const float* __restrict__ tin,
         // its DoG is used downstream)
         if (pair) {
             if (dst) *reinterpret_cast<f2v*>(dst + off) = acc;
-            if (dog) *reinterpret_cast<f2v*>(dog + off) = acc - centre[o];
         } else {
             if (dst) dst[off] = acc.x;
-            if (dog) dog[off] = acc.x - centre[o].x;
         }
         // nearest 1/2: pixel (2x, 2y) for cv::resize INTER_NEAREST, (2x + 1,
         // 2y + 1) for image's Nearest; gy parity == o parity
@@ -235,7 +219,6 @@ __device__ __forceinline__ void load_window_border(float* __restrict__ tin, cons
 template <int R, int TH, int P>
 __global__ __launch_bounds__(256) void k_blur(const float* __restrict__ src, size_t src_img_stride,
                                               float* __restrict__ dst, size_t dst_img_stride,
-                                              float* __restrict__ dog, size_t dog_img_stride,
                                               float* __restrict__ nxt, size_t nxt_img_stride, int pitch_n, int wn,
                                               int hn, int W, int H, int pitch, const BlurTaps taps, int ty0) {
     using G = BlurGeom<R, TH>;
@@ -273,8 +256,7 @@ __global__ __launch_bounds__(256) void k_blur(const float* __restrict__ src, siz
     }
     __syncthreads();
     blur_tile_compute<R, TH, P>(tin, th, taps, x0, y0, W, H, pitch, dst ? dst + b * dst_img_stride : nullptr,
-                             dog ? dog + b * dog_img_stride : nullptr, nxt ? nxt + b * nxt_img_stride : nullptr,
-                             pitch_n, wn, hn);
+                             nxt ? nxt + b * nxt_img_stride : nullptr, pitch_n, wn, hn);
 }
 
 // ---------------------------------------------------------------------------
@@ -1139,7 +1121,7 @@ __global__ __launch_bounds__(256) void k_seed(const uint8_t* __restrict__ frames
         }
     }
     __syncthreads();
-    blur_tile_compute<R, TH>(tin, th, taps, x0, y0, W, H, pitch, dst + b * dst_img_stride, nullptr, nullptr, 0, 0,
+    blur_tile_compute<R, TH>(tin, th, taps, x0, y0, W, H, pitch, dst + b * dst_img_stride, nullptr, 0, 0,
                              0);
 }
 
@@ -1684,7 +1666,7 @@ __global__ __launch_bounds__(256) void k_seed_ip(const uint8_t* __restrict__ fra
     }
     __syncthreads();
     blur_tile_compute<R, TH, kProfileImageproc>(tin, lds, taps, x0, y0, W, H, pitch, dst + b * dst_img_stride, nullptr,
-                                                nullptr, 0, 0, 0);
+                                                0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -1702,11 +1684,11 @@ static void launch_blur_r(const BlurLaunch& L, hipStream_t st) {
     dim3 grid((L.W + G::TW - 1) / G::TW, ty1 - ty0, L.n_img);
     if (L.profile == kProfileImageproc)
         klaunch((k_blur<R, TH, kProfileImageproc>), grid, dim3(256), st, L.src, L.src_img_stride, L.dst,
-                           L.dst_img_stride, L.dog, L.dog_img_stride, L.nxt, L.nxt_img_stride, L.pitch_n, L.wn, L.hn,
+                           L.dst_img_stride, L.nxt, L.nxt_img_stride, L.pitch_n, L.wn, L.hn,
                            L.W, L.H, L.pitch, L.taps, ty0);
     else
         klaunch((k_blur<R, TH, kProfileOpenCV>), grid, dim3(256), st, L.src, L.src_img_stride, L.dst,
-                           L.dst_img_stride, L.dog, L.dog_img_stride, L.nxt, L.nxt_img_stride, L.pitch_n, L.wn, L.hn,
+                           L.dst_img_stride, L.nxt, L.nxt_img_stride, L.pitch_n, L.wn, L.hn,
                            L.W, L.H, L.pitch, L.taps, ty0);
 }
 
@@ -1796,7 +1778,7 @@ int launch_blur_pair(int ra, int rb, const BlurLaunch& A, const BlurLaunch& B, h
     // A: G_{s-1} -> G_s, B: G_s -> G_{s+1} of one octave arena (same geometry
     // and image stride); whole planes, no DoG; at most one of them writes the
     // next octave's base (B: blurs 2, 3 of octave 0 after k_seed_pair)
-    const bool ok = A.profile == B.profile && !A.dog && !B.dog && !(A.nxt && B.nxt) && A.y1 <= A.y0 &&
+    const bool ok = A.profile == B.profile && !(A.nxt && B.nxt) && A.y1 <= A.y0 &&
                     B.y1 <= B.y0 && A.dst && B.dst && B.src == A.dst && A.W == B.W && A.H == B.H &&
                     A.pitch == B.pitch && A.src_img_stride == A.dst_img_stride &&
                     B.src_img_stride == A.src_img_stride && B.dst_img_stride == A.src_img_stride && A.W >= 64 &&
@@ -1823,7 +1805,7 @@ int launch_blur_pair(int ra, int rb, const BlurLaunch& A, const BlurLaunch& B, h
 int launch_blur(int R, const BlurLaunch& L, hipStream_t st, const PathOpts& o) {
     // the strip kernel: materialised G_s, no DoG plane (the batch path), one
     // reflection per border (W, H > R), planes addressable by 32-bit offsets
-    if (L.dst && !L.dog && R <= kStripMaxR && L.W > R && L.H > R &&
+    if (L.dst && R <= kStripMaxR && L.W > R && L.H > R &&
         (uint64_t)L.H * (uint64_t)L.pitch * 4 < (1ull << 31) && !o.tile_blur) {
         switch (R) {
 #define CASE(r) \
@@ -1926,7 +1908,7 @@ int launch_seed_pair(int rs, int rb, const SeedLaunch& S, const BlurLaunch& B, h
     // pair's (whole planes, B = blur 1 of the seed's plane, same arena)
     const bool ok = S.W == 2 * S.sw && S.H == 2 * S.sh && S.W >= 160 && S.H >= 64 &&
                     (uint64_t)S.H * (uint64_t)S.pitch * 4 < (1ull << 31) && S.y1 <= S.y0 && B.y1 <= B.y0 &&
-                    B.profile == S.profile && B.src == S.dst && B.dst && !B.dog && !B.nxt && B.W == S.W &&
+                    B.profile == S.profile && B.src == S.dst && B.dst && !B.nxt && B.W == S.W &&
                     B.H == S.H && B.pitch == S.pitch && B.src_img_stride == S.dst_img_stride &&
                     B.dst_img_stride == S.dst_img_stride && !o.tile_blur && o.pair && o.seed_pair;
     if (!ok) return -1;

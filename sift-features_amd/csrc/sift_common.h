@@ -11,15 +11,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sift_consts.h"
+
 namespace siftmi {
 
 // packed f32 pairs / quads (v_pk_* arithmetic, 8- and 16-byte LDS accesses)
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 
-constexpr int kScalesPerOctave = 3;                  // src/lib.rs:92
-constexpr int kImagesPerOctave = kScalesPerOctave + 3;  // 6 Gaussian images (src/lib.rs:218-221)
-constexpr int kDogPerOctave = kScalesPerOctave + 2;     // 5 DoG images (src/lib.rs:277)
 constexpr float kContrastThreshold = 0.04f;          // src/lib.rs:93
 constexpr float kEdgeThreshold = 10.0f;              // src/lib.rs:94
 constexpr int kImageBorder = 5;                      // src/lib.rs:100
@@ -31,7 +30,6 @@ constexpr int kDescBins = 8;                         // src/lib.rs:110
 constexpr int kDescSize = 128;                       // src/lib.rs:111
 constexpr float kOriPeakRatio = 0.8f;                // src/lib.rs:297
 constexpr int kMaxInterpSteps = 5;                   // src/lib.rs:516
-constexpr int kMaxBlurRadius = 31;                   // taps <= 63 per pass
 
 // Emission key layout (see include/sift_mi.h, sift_mi_fetch_keys).  x_init
 // and y_init are octave coordinates; octave 0 is the 2x seed, so a 16384-px
@@ -89,11 +87,6 @@ __device__ __forceinline__ void desc_rotation(float angle, float& s, float& c) {
 // Output keypoint (include/sift_mi.h sift_mi_keypoint).
 struct OutKp {
     float x, y, size, angle, response;
-};
-
-// Blur taps, centre-indexed: k[0] = centre, k[t] = tap at distance t.
-struct BlurTaps {
-    float k[kMaxBlurRadius + 1];
 };
 
 // ---------------------------------------------------------------------------

@@ -74,8 +74,6 @@ struct BlurLaunch {
     size_t src_img_stride;
     float* dst;
     size_t dst_img_stride;
-    float* dog;  // may be null
-    size_t dog_img_stride;
     float* nxt;  // may be null: next octave base (nearest 1/2)
     size_t nxt_img_stride;
     int pitch_n, wn, hn;
@@ -106,7 +104,7 @@ struct SeedLaunch {
 };
 
 
-// Host wait for an event (host.cpp): spins ~1 ms, then polls with short
+// Host wait for an event (pipeline.cpp): spins ~1 ms, then polls with short
 // sleeps, so a thread waiting for a multi-ms chunk does not hold a CPU the
 // decode threads (or a CPU quota) need.
 hipError_t host_wait_event(hipEvent_t e);
@@ -147,11 +145,8 @@ int tail_octave_start(const int* ow, const int* oh, int n_oct, const int* radii)
 void launch_octave_tail(const TailLaunch& L, hipStream_t st);
 
 // pyramid.hip
-// The next kernel a pyramid launcher enqueues from this host thread signals
-// e on completion (no marker packet of its own); launch_done_pending() is
-// true while no launch has taken it (the caller then clears it and records e)
-void set_launch_done_event(hipEvent_t e);
-bool launch_done_pending();
+// (a launcher's next kernel carries the completion event of a LaunchDoneEvent
+// in scope: launch_ext.h)
 int launch_blur(int radius, const BlurLaunch& L, hipStream_t st, const PathOpts& o = PathOpts{});
 // two consecutive blurs of an octave (A then B, B.src == A.dst) in one pass;
 // -1 when the pair kernel does not apply (the caller launches them singly)
@@ -212,6 +207,16 @@ int launch_blur_detect(int R, BlurDetectLaunch& L, hipStream_t st, const PathOpt
 // whether launch_blur_detect would launch (the same test, nothing enqueued)
 bool blur_detect_applies(int R, const BlurDetectLaunch& L, const PathOpts& o = PathOpts{});
 
+// Device tables of one lane's pyramid, indexed by octave: what the keypoint
+// stages need to address any Gaussian of any frame of the chunk.
+struct OctaveView {
+    const float* const* gauss;  // octave G_0 bases (the DoG is formed from G_0..G_5 where it is read)
+    const size_t* img_stride;   // floats between frames
+    const int* ow;
+    const int* oh;
+    const int* opitch;
+};
+
 // Stage sizes live in device counters (no host round trip between stages):
 // every consumer reads its count from device memory, clamps it to the buffer
 // bound, and walks the items with a grid-stride loop.
@@ -225,12 +230,8 @@ struct RefineLaunch {
     // accepted keypoint's patch (+-patch rows) leaves them
     uint32_t* band_flag;
     int band_r, band_n, band_margin, band_patch;
-    const float* const* gauss;   // device array [n_octaves] of octave G_0 bases (D formed from G)
-    const size_t* g_img_stride;  // device array [n_octaves]
-    const int* ow;
-    const int* oh;
-    const int* opitch;
-    int n_oct;  // entries of the device arrays above
+    OctaveView oct;
+    int n_oct;  // entries of oct's device arrays
     int img_base;
     ExtRec* out;
     uint32_t* counter;
@@ -252,11 +253,7 @@ struct OrientLaunch {
     const uint32_t* n_ext;  // device count, clamped to ext_cap
     const uint32_t* n_ext_hi;  // two-ended ext (RefineLaunch::counter_hi; null: off): back-end count
     uint32_t ext_cap;
-    const float* const* gauss;     // device array [n_octaves] of octave G bases
-    const size_t* gauss_img_stride;  // device array [n_octaves]
-    const int* ow;                 // device arrays [n_octaves]
-    const int* oh;
-    const int* opitch;
+    OctaveView oct;
     KpRec* out;
     uint32_t* counter;
     int img_base;
@@ -320,11 +317,7 @@ struct DescLaunch {
     uint32_t* work;       // kDescQueues zeroed work counters, kDescQueueStride words apart: waves
                           // take keypoints dynamically (costs vary ~20x)
     uint64_t key_base;    // added to the emission keys (frame offset of the chunk)
-    const float* const* gauss;
-    const size_t* gauss_img_stride;
-    const int* ow;
-    const int* oh;
-    const int* opitch;
+    OctaveView oct;
     int img_base;
     OutKp* out_kp;     // may be null
     uint64_t* out_key; // may be null

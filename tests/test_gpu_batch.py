@@ -114,7 +114,7 @@ def test_device_resident_results(pkg, ctx, chunk):
     path); copied back they equal the host-fetched batch, chunked or not.
     chunk -1: the whole batch in one chunk, -2: a single frame -- one chunk,
     whose results are handed out as the slot's own output buffers (no copy;
-    host.cpp res_slot), then a fetch=True call on the same context must
+    pipeline.cpp res_slot), then a fetch=True call on the same context must
     return its own results, not the slot's stale ones."""
     import torch
     fr = _frames()

@@ -11,7 +11,7 @@
 * config #4, one GPU's shard: bench.py's exact call (128 x 1920x1080, auto
   chunks -- one of 128, or two of 64 under chunk_mode 0 -- results kept in
   HBM), 2 frames vs the oracle, every frame vs per-frame `sift()`;
-* the stage-bound overflow re-run (host.cpp finalize_chunk rc == 1): with
+* the stage-bound overflow re-run (pipeline.cpp finalize_chunk rc == 1): with
   path option bound_shrink every chunk enqueued before a high-water mark exists
   overflows; the re-run chunks must equal per-frame results.
 Configs #1 (bird_small) and #5 (8192^2) are covered by test_gpu_parity /

@@ -190,7 +190,7 @@ def test_pattern_batch_mixed(pkg, oracle, contexts, profile, chunking, limit):
 @pytest.mark.parametrize("name", ["checker5", "white"])
 def test_pattern_first_call_bounds(pkg, oracle, name, profile, entry, shrink):
     """A fresh context has no high-water marks: its buffers are sized by
-    chunk_bounds' first-call estimates (host.cpp: 1.3 * sum(px) / 256
+    chunk_bounds' first-call estimates (pipeline.cpp: 1.3 * sum(px) / 256
     candidates, / 512 extrema, / 384 keypoints, each + 1024; bound_shrink =
     1000 divides them and drops the slack).  checker5 (OpenCV profile) has
     3188 keypoints against a bound of 1245; `white` has tens of thousands of

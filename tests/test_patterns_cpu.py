@@ -190,7 +190,7 @@ def test_plateau_candidates(oracle, name):
     and `stars_inv` have 31 328 and 23 825 there (the half of `step` that is
     exactly 0 fails |val| > 0).  Every count is far above a fresh context's
     candidate bound for a 97 x 161 frame, 1.3 * sum(px) / 256 + 1024 = 1446
-    (host.cpp chunk_bounds), which is what test_pattern_first_call_bounds
+    (pipeline.cpp chunk_bounds), which is what test_pattern_first_call_bounds
     relies on."""
     counts = []
     for profile in (0, 1):

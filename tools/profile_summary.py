@@ -86,7 +86,7 @@ tot = sum(v[1] for k, v in agg.items() if k.startswith("k_") or "rocprim" in k)
 # ---- the serialised stage-timing pass of bench.py (the roofline's HIP-event
 # figure): chunks start at k_seed*; a chunk is every kernel started between its
 # seed and the next one, on any stream (the lane's stream and its aux stream:
-# octave overlap, host.cpp run_pyramid).  A chunk is serialised when it starts
+# octave overlap, pipeline.cpp PyramidRun).  A chunk is serialised when it starts
 # after the previous chunk's kernels end and ends before the next seed (the
 # one-lane pass; the two-lane pass overlaps neighbour chunks).  One warmup step
 # precedes the timed steps.

@@ -32,7 +32,7 @@ struct DogViewOld {
 __device__ __forceinline__ bool interpolate_old(const DogViewOld& dv, int W, int H, int pitch, int& scale, int& x, int& y,
                                             float& os, float& ox, float& oy, uint32_t* band_flag, int vlo, int vhi) {
     for (int it = 0; it < kMaxInterpSteps; it++) {
-        // row bands with a restricted pyramid (host.cpp run_pyramid): the
+        // row bands with a restricted pyramid (pipeline.cpp PyramidRun): the
         // rows read here must be computed ones, else the host recomputes the
         // band on the whole-frame pyramid
         if (band_flag && (y - 1 < vlo || y + 1 >= vhi)) atomicOr(band_flag, 1u);
@@ -88,8 +88,8 @@ __device__ __forceinline__ bool refine_one_old(const RefineLaunch& L, uint64_t k
     const int s_in = (int)((key >> kKeyScaleShift) & 3);
     const int y = (int)((key >> kKeyYShift) & kKeyCoordMask);
     const int x = (int)((key >> kKeyXShift) & kKeyCoordMask);
-    const int W = L.ow[o], H = L.oh[o], pitch = L.opitch[o];
-    const DogViewOld dv{as_global(L.gauss[o]) + (size_t)(b - L.img_base) * L.g_img_stride[o], (size_t)pitch * H};
+    const int W = L.oct.ow[o], H = L.oct.oh[o], pitch = L.oct.opitch[o];
+    const DogViewOld dv{as_global(L.oct.gauss[o]) + (size_t)(b - L.img_base) * L.oct.img_stride[o], (size_t)pitch * H};
     int sc = s_in, xi = x, yi = y;
     float os, ox, oy;
     int vlo = 0, vhi = H;  // rows of this octave's Gaussians that are exact
@@ -161,7 +161,7 @@ __device__ __forceinline__ bool interpolate_r5a(const gfloat* g0, size_t P, int 
                                             int& y, float& os, float& ox, float& oy, Nbhd& n, uint32_t* band_flag,
                                             int vlo, int vhi) {
     for (int it = 0; it < kMaxInterpSteps; it++) {
-        // row bands with a restricted pyramid (host.cpp run_pyramid): the
+        // row bands with a restricted pyramid (pipeline.cpp PyramidRun): the
         // rows read here must be computed ones, else the host recomputes the
         // band on the whole-frame pyramid
         if (band_flag && (y - 1 < vlo || y + 1 >= vhi)) atomicOr(band_flag, 1u);
@@ -217,8 +217,8 @@ __device__ __forceinline__ bool refine_one_r5a(const RefineLaunch& L, uint64_t k
     const int s_in = (int)((key >> kKeyScaleShift) & 3);
     const int y = (int)((key >> kKeyYShift) & kKeyCoordMask);
     const int x = (int)((key >> kKeyXShift) & kKeyCoordMask);
-    const int W = L.ow[o], H = L.oh[o], pitch = L.opitch[o];
-    const gfloat* g0 = as_global(L.gauss[o]) + (size_t)(b - L.img_base) * L.g_img_stride[o];
+    const int W = L.oct.ow[o], H = L.oct.oh[o], pitch = L.oct.opitch[o];
+    const gfloat* g0 = as_global(L.oct.gauss[o]) + (size_t)(b - L.img_base) * L.oct.img_stride[o];
     const size_t P = (size_t)pitch * H;
     int sc = s_in, xi = x, yi = y;
     float os, ox, oy;
@@ -364,7 +364,7 @@ int main(int argc, char** argv) {
     float* g = nullptr;
     CK(hipMalloc(&g, stride * n * sizeof(float)));
     hipLaunchKernelGGL(k_fill_smooth, dim3((W + 63) / 64, (H + 63) / 64, n), dim3(256), 0, 0, g, W, H, pitch, stride, n);
-    // OpenCV octave sigmas (host.cpp octave_sigmas / cv_blur_taps): radii 5, 6, 8, 10, 13
+    // OpenCV octave sigmas (geometry.cpp octave_sigmas / cv_blur_taps): radii 5, 6, 8, 10, 13
     const double sig[6] = {0, 1.2262735, 1.5450078, 1.9465878, 2.4525469, 3.0900155};
     BlurTaps taps[6]{};
     int rad[6]{};
@@ -525,11 +525,7 @@ int main(int argc, char** argv) {
     R.cand = cand;
     R.n_cand = cnt;
     R.cand_cap = nc;
-    R.gauss = dg;
-    R.g_img_stride = dgs;
-    R.ow = dw;
-    R.oh = dh;
-    R.opitch = dp;
+    R.oct = OctaveView{dg, dgs, dw, dh, dp};
     R.n_oct = 1;
     R.out = ext;
     R.counter = cnt + 1;

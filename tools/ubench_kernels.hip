@@ -53,10 +53,10 @@ __global__ void k_fill(float* p, size_t n) {
     }
 }
 
-// stride = distance between frames (floats); arena layout puts G_{s-1}, G_s,
-// D_{s-1} of one frame inside an 11-plane octave arena, like the product.
+// stride = distance between frames (floats); arena layout puts G_{s-1}, G_s
+// of one frame inside an 11-plane octave arena.
 template <int R, int TH>
-float time_blur(const float* src, float* dst, float* dog, size_t stride, int W, int H, int pitch, int nimg,
+float time_blur(const float* src, float* dst, size_t stride, int W, int H, int pitch, int nimg,
                 int reps) {
     using G = BlurGeom<R, TH>;
     BlurTaps taps{};
@@ -64,7 +64,7 @@ float time_blur(const float* src, float* dst, float* dog, size_t stride, int W, 
     const int tx = (W + G::TW - 1) / G::TW, ty = (H + G::TH - 1) / G::TH;
     dim3 grid(tx, ty, nimg);
     auto go = [&]() {
-        hipLaunchKernelGGL((k_blur<R, TH, kProfileOpenCV>), grid, dim3(256), 0, 0, src, stride, dst, stride, dog, stride,
+        hipLaunchKernelGGL((k_blur<R, TH, kProfileOpenCV>), grid, dim3(256), 0, 0, src, stride, dst, stride,
                            (float*)nullptr, (size_t)0, 0, 0, 0, W, H, pitch, taps, 0);
     };
     go();
@@ -120,7 +120,7 @@ void bench_blur_strip(int N) {
     std::printf("blur G_{s-1} -> G_s, %d x %dx%d (arena, random): ms, GB/s at 8 B/px\n", N, W, H);
 #define B(R, TH)                                                                                                  \
     {                                                                                                             \
-        const float mt = time_blur<R, TH>(base, base + plane, nullptr, stride, W, H, pitch, N, 5);                 \
+        const float mt = time_blur<R, TH>(base, base + plane, stride, W, H, pitch, N, 5);                 \
         const float ms = time_blur_strip<R>(base, base + plane, stride, W, H, pitch, N, 5);                       \
         std::printf("  R=%2d tile(TH=%d) %8.3f ms %7.1f GB/s | strip %8.3f ms %7.1f GB/s\n", R, TH, mt,            \
                     bytes / (mt * 1e-3) / 1e9, ms, bytes / (ms * 1e-3) / 1e9);                                      \
@@ -133,14 +133,13 @@ void bench_blur_strip(int N) {
 void bench_blur(int N, bool arena, bool random) {
     const int W = 3840, H = 2160, pitch = 3840;
     const size_t plane = (size_t)pitch * H;
-    float *base, *s, *d, *g;
+    float *base, *s, *d;
     size_t stride;
     if (arena) {
         CK(hipMalloc(&base, plane * 11 * N * 4));
         stride = plane * 11;
         s = base;
         d = base + plane;
-        g = base + 6 * plane;
         if (random) hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, base, plane * 11 * N);
         else CK(hipMemset(base, 0, plane * 11 * N * 4));
     } else {
@@ -148,17 +147,16 @@ void bench_blur(int N, bool arena, bool random) {
         stride = plane;
         s = base;
         d = base + plane * N;
-        g = base + 2 * plane * N;
         if (random) hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, base, plane * 3 * N);
         else CK(hipMemset(base, 0, plane * 3 * N * 4));
     }
     CK(hipDeviceSynchronize());
-    const double bytes = 12.0 * W * H * N;  // read G_{s-1}, write G_s + D_{s-1}
-    std::printf("blur octave-0 batch (%d x %dx%d, %s layout, %s data): ms, effective GB/s (12 B/px)\n", N, W, H,
+    const double bytes = 8.0 * W * H * N;  // read G_{s-1}, write G_s
+    std::printf("blur octave-0 batch (%d x %dx%d, %s layout, %s data): ms, effective GB/s (8 B/px)\n", N, W, H,
                 arena ? "arena" : "planar", random ? "random" : "zero");
 #define B(R, TH)                                                                                         \
     {                                                                                                    \
-        const float ms = time_blur<R, TH>(s, d, g, stride, W, H, pitch, N, 5);                           \
+        const float ms = time_blur<R, TH>(s, d, stride, W, H, pitch, N, 5);                           \
         std::printf("  R=%2d TH=%2d %8.3f ms %8.1f GB/s\n", R, TH, ms, bytes / (ms * 1e-3) / 1e9);        \
     }
     B(5, 32) B(5, 64) B(6, 32) B(6, 64) B(8, 32) B(8, 64) B(10, 64) B(10, 128) B(13, 64) B(13, 128)
@@ -853,11 +851,7 @@ int main(int argc, char** argv) {
     uint32_t* d_work;
     CK(hipMalloc(&d_work, kDescWorkWords * 4));
     L.work = d_work;
-    L.gauss = d_g;
-    L.gauss_img_stride = d_gs;
-    L.ow = d_w;
-    L.oh = d_h;
-    L.opitch = d_p;
+    L.oct = OctaveView{d_g, d_gs, d_w, d_h, d_p};
     L.out_desc = d_desc;
     const int reps = 5;
     std::printf("describe n=%d\n", NKP);
