@@ -249,7 +249,14 @@ int sift_mi_match_descriptors(sift_mi_ctx* ctx, const uint8_t* query, size_t n_q
  * sift_mi_jpeg_dims: frame size from the headers (host only, no device).
  * sift_mi_decode_jpeg: luma into out (row stride out_stride), a host buffer,
  * or device memory when out_on_device != 0 (ordered on the context stream;
- * the call returns once the frame is written). */
+ * the call returns once the frame is written).
+ * Limits: the decode calls refuse a frame with a side above 16384 px (what
+ * sift_mi_extract takes) with SIFT_MI_EINVAL, before anything is allocated
+ * from the header; sift_mi_jpeg_dims still reports such a size.  Malformed
+ * input is SIFT_MI_EINVAL, an unsupported frame (progressive, 12-bit, 4
+ * components, sampling factors above 2, vertical-only chroma subsampling,
+ * several scans) SIFT_MI_EUNSUPPORTED, a failed host or device allocation
+ * SIFT_MI_ENOMEM; no C++ exception leaves these calls. */
 int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height);
 int sift_mi_decode_jpeg(sift_mi_ctx* ctx, const uint8_t* data, size_t len, uint8_t* out, size_t out_stride,
                         int out_on_device);

@@ -3,6 +3,7 @@
 // pool and the stand-alone Processing ops.
 #include <cmath>
 #include <mutex>
+#include <new>
 #include <thread>
 
 #include "host_internal.h"
@@ -127,6 +128,26 @@ int ip_resize_op(sift_mi_ctx* c, const float* src, uint32_t w, uint32_t h, uint3
     launch_ip_resize_f32(a.p, (int)w, (int)h, tab.xl.p, tab.xw.p, tab.xtaps, tab.yl.p, tab.yw.p, tab.ytaps, t.p, b.p,
                          (int)dw, (int)dh, c->stream);
     return download(dst, b, (size_t)dw * dh, c->stream);
+}
+
+// No C++ exception leaves the JPEG entry points: the host side sizes vectors
+// from the stream's headers.
+template <class F>
+int jpeg_guard(F&& body) {
+    int rc = SIFT_MI_EINVAL;
+    const char* what = "JPEG: exception";
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        rc = SIFT_MI_ENOMEM;
+        what = "JPEG: host allocation failed";
+    } catch (...) {
+    }
+    try {
+        return fail(rc, what);
+    } catch (...) {  // not even the message could be stored
+        return rc;
+    }
 }
 }  // namespace
 
@@ -540,22 +561,26 @@ int sift_mi_match_descriptors(sift_mi_ctx* c, const uint8_t* query, size_t nq, c
 
 int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height) {
     if (!data || !width || !height) return fail(SIFT_MI_EINVAL, "bad arguments");
-    std::string err;
-    const int rc = jpeg_dims(data, len, width, height, err);
-    return rc ? fail(rc, err) : 0;
+    return jpeg_guard([&]() -> int {
+        std::string err;
+        const int rc = jpeg_dims(data, len, width, height, err);
+        return rc ? fail(rc, err) : 0;
+    });
 }
 
 int sift_mi_decode_jpeg(sift_mi_ctx* c, const uint8_t* data, size_t len, uint8_t* out, size_t out_stride,
                         int out_on_device) {
     if (!c || !data || !out) return fail(SIFT_MI_EINVAL, "bad arguments");
-    uint32_t w = 0, h = 0;
-    std::string err;
-    int rc = jpeg_dims(data, len, &w, &h, err);
-    if (rc) return fail(rc, err);
-    if (out_stride < w) return fail(SIFT_MI_EINVAL, "out_stride < width");
-    CHK(set_device(c));
-    rc = jpeg_decode_luma(data, len, out, out_stride, out_on_device != 0, c->stream, err);
-    return rc ? fail(rc, err) : 0;
+    return jpeg_guard([&]() -> int {
+        uint32_t w = 0, h = 0;
+        std::string err;
+        int rc = jpeg_dims(data, len, &w, &h, err);
+        if (rc) return fail(rc, err);
+        if (out_stride < w) return fail(SIFT_MI_EINVAL, "out_stride < width");
+        CHK(set_device(c));
+        rc = jpeg_decode_luma(data, len, out, out_stride, out_on_device != 0, c->stream, err);
+        return rc ? fail(rc, err) : 0;
+    });
 }
 
 int sift_mi_decode_jpeg_batch(sift_mi_ctx* c, const uint8_t* const* data, const size_t* len, uint32_t n,
@@ -564,6 +589,7 @@ int sift_mi_decode_jpeg_batch(sift_mi_ctx* c, const uint8_t* const* data, const 
     for (uint32_t i = 0; i < n; i++)
         if (!data[i]) return fail(SIFT_MI_EINVAL, "null JPEG");
     if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    return jpeg_guard([&]() -> int {
     CHK(set_device(c));
     std::string err;
     // The reconstruction kernels run on a high-priority stream of their own
@@ -588,6 +614,7 @@ int sift_mi_decode_jpeg_batch(sift_mi_ctx* c, const uint8_t* const* data, const 
     }
     const int rc = jpeg_decode_batch(data, len, n, d_frames, frame_pitch, row_stride, threads, st, c->jpeg, err);
     return rc ? fail(rc, err) : 0;
+    });
 }
 
 int sift_mi_get_stats(sift_mi_ctx* c, sift_mi_stats* out) {

@@ -204,6 +204,7 @@ int parse(const uint8_t* d, size_t n, Header& H, std::string& err) {
     while (p + 4 <= n) {
         if (d[p] != 0xFF) return err = "JPEG: marker expected", SIFT_MI_EINVAL;
         while (p + 1 < n && d[p + 1] == 0xFF) p++;  // fill bytes
+        if (p + 1 >= n) return err = "JPEG: truncated segment", SIFT_MI_EINVAL;  // the buffer ends in fill bytes
         const int m = d[p + 1];
         p += 2;
         if (m == 0xD9) break;
@@ -612,7 +613,12 @@ void qtables(const Header& H, int32_t* q) {  // 3 x 64, components' order
     for (int k = 0; k < H.nc; k++) std::memcpy(q + 64 * k, H.q[H.c[k].tq], 64 * sizeof(int32_t));
 }
 
+// Called by both decode paths straight after parse(), before any buffer is
+// sized from the header.
 int check_support(const Header& H, const Geom& g, std::string& err) {
+    // what sift() takes (pipeline.cpp); also bounds the host and device buffers of a decode
+    if ((uint32_t)H.w > kMaxFrameSide || (uint32_t)H.h > kMaxFrameSide)
+        return err = "JPEG: frame larger than 16384 px", SIFT_MI_EINVAL;
     for (int k = 0; k < H.nc; k++)  // h2v1, h2v2 and full-size chroma (the restatement's cases)
         if (H.nc == 3 && g.hmax / H.c[k].h == 1 && g.vmax / H.c[k].v == 2)
             return err = "JPEG: vertical-only chroma subsampling", SIFT_MI_EUNSUPPORTED;
@@ -793,8 +799,12 @@ int jpeg_decode_batch(const uint8_t* const* data, const size_t* len, uint32_t n,
     const int T = std::max(1, std::min<int>(threads, (int)n));
     std::vector<std::thread> pool;
     pool.reserve(T);
-    for (int t = 0; t < T; t++) pool.emplace_back(work);
-    bool ok = true;
+    bool ok = true, spawned = true;
+    try {
+        for (int t = 0; t < T; t++) pool.emplace_back(work);
+    } catch (...) {  // std::system_error: no more threads.  Stop and join those that started.
+        spawned = ok = false;
+    }
     for (uint32_t ch = 0; ch < n_chunks && ok; ch++) {
         const uint32_t c0 = ch * C, m = std::min(C, n - c0), k = ch & 1;
         {
@@ -829,6 +839,7 @@ int jpeg_decode_batch(const uint8_t* const* data, const size_t* len, uint32_t n,
     cv.notify_all();
     for (auto& th : pool) th.join();
     const bool synced = hipStreamSynchronize(st) == hipSuccess;
+    if (!spawned) return err = "JPEG batch: cannot start host threads", SIFT_MI_ENOMEM;
     if (trc) return err = terr, trc;
     if (!ok || !synced) return err = "JPEG batch: HIP error", SIFT_MI_EHIP;
     return 0;

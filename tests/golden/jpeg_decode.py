@@ -257,21 +257,35 @@ def _idct_islow(c):
     return np.clip((px & 1023) + 128 if False else px + 128, 0, 255).reshape(c.shape[:-1] + (8, 8))
 
 
-def _idct_stb(c, row_bias=65536 + (128 << 17)):
+def _idct_stb(c, row_bias=65536 + (128 << 17), peak=None):
     """stb_image stbi__idct_block (12-bit fixed point).  `row_bias` is the
-    rounding + level-shift term of the row pass."""
+    rounding + level-shift term of the row pass.  `peak`, a list, receives
+    the largest magnitude among the intermediates (the arithmetic here is
+    int64; the decoders restated compute in 32 bits, so a caller can assert
+    that nothing reached 2^31)."""
     def f2f(x):
         return int(x * 4096 + 0.5)
 
+    def note(*vals):
+        if peak is not None:
+            peak.append(max(int(np.abs(v).max()) for v in vals if np.size(v)))
+
     def one_d(s):
+        x0, x1, x2, x3, t0, t1, t2, t3 = one_d_(s)
+        note(x0, x1, x2, x3, t0, t1, t2, t3)
+        return x0, x1, x2, x3, t0, t1, t2, t3
+
+    def one_d_(s):
         s0, s1, s2, s3, s4, s5, s6, s7 = [s[..., i] for i in range(8)]
         p2, p3 = s2, s6
         p1 = (p2 + p3) * f2f(0.5411961)
         t2 = p1 + p3 * f2f(-1.847759065)
         t3 = p1 + p2 * f2f(0.765366865)
+        note(p1, t2, t3, p3 * f2f(-1.847759065), p2 * f2f(0.765366865))
         p2, p3 = s0, s4
         t0 = (p2 + p3) * 4096
         t1 = (p2 - p3) * 4096
+        note(t0, t1)
         x0, x3, x1, x2 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
         t0, t1, t2, t3 = s7, s5, s3, s1
         p3, p4, p1, p2 = t0 + t2, t1 + t3, t0 + t3, t1 + t2
@@ -281,6 +295,7 @@ def _idct_stb(c, row_bias=65536 + (128 << 17)):
         p2 = p5 + p2 * f2f(-2.562915447)
         p3 = p3 * f2f(-1.961570560)
         p4 = p4 * f2f(-0.390180644)
+        note(p5, t0, t1, t2, t3, p1, p2, p3, p4, p1 + p4, p2 + p3, p2 + p4, p1 + p3)
         t3 += p1 + p4
         t2 += p2 + p3
         t1 += p2 + p4
@@ -291,6 +306,7 @@ def _idct_stb(c, row_bias=65536 + (128 << 17)):
     cols = np.transpose(blk, (0, 2, 1))  # [n][u][v]
     x0, x1, x2, x3, t0, t1, t2, t3 = one_d(cols)
     x0, x1, x2, x3 = x0 + 512, x1 + 512, x2 + 512, x3 + 512
+    note(x0 + t3, x1 + t2, x2 + t1, x3 + t0, x3 - t0, x2 - t1, x1 - t2, x0 - t3)
     v = np.stack([(x0 + t3) >> 10, (x1 + t2) >> 10, (x2 + t1) >> 10, (x3 + t0) >> 10,
                   (x3 - t0) >> 10, (x2 - t1) >> 10, (x1 - t2) >> 10, (x0 - t3) >> 10], axis=-1)
     ac_zero = np.all(cols[..., 1:] == 0, axis=-1)
@@ -298,17 +314,23 @@ def _idct_stb(c, row_bias=65536 + (128 << 17)):
     rows = np.transpose(v, (0, 2, 1))  # [n][y][u]
     x0, x1, x2, x3, t0, t1, t2, t3 = one_d(rows)
     x0, x1, x2, x3 = x0 + row_bias, x1 + row_bias, x2 + row_bias, x3 + row_bias
+    note(x0 + t3, x1 + t2, x2 + t1, x3 + t0, x3 - t0, x2 - t1, x1 - t2, x0 - t3)
     o = np.stack([(x0 + t3) >> 17, (x1 + t2) >> 17, (x2 + t1) >> 17, (x3 + t0) >> 17,
                   (x3 - t0) >> 17, (x2 - t1) >> 17, (x1 - t2) >> 17, (x0 - t3) >> 17], axis=-1)
     return np.clip(o, 0, 255).reshape(c.shape[:-1] + (8, 8))
 
 
-def _idct_zune(c, row_bias=512 + 65536 + (128 << 17)):
+def _idct_zune(c, row_bias=512 + 65536 + (128 << 17), peak=None):
     """zune-jpeg's integer IDCT: stb_image's arithmetic with the row-pass
     bias 512 + 65536 + (128 << 17) (the column pass's 512 carried into the
     row pass), plus a whole-block shortcut: a block whose 63 AC coefficients
-    are zero becomes (DC >> 3) + 128 (no rounding term)."""
-    out = _idct_stb(c, row_bias)
+    are zero becomes (DC >> 3) + 128 (no rounding term).  `peak`: see
+    _idct_stb; on return it holds one number, the largest intermediate
+    magnitude over all blocks (those a shortcut replaces included, so an
+    upper bound)."""
+    out = _idct_stb(c, row_bias, peak)
+    if peak is not None:
+        peak[:] = [max(peak)]
     flat = c.reshape(-1, 64)
     dc_only = np.all(flat[:, 1:] == 0, axis=1).reshape(c.shape[:-1])
     dcv = np.clip((c[..., 0] >> 3) + 128, 0, 255)
