@@ -145,7 +145,9 @@ int sift_mi_set_keep_on_device(sift_mi_ctx* ctx, int keep);
 
 /* Device pointers of the last batch's results (keep_on_device = 1): the
  * keypoints and descriptors of every frame, concatenated in frame order
- * (frame i at offsets[i] .. offsets[i+1]); valid until the next call. */
+ * (frame i at offsets[i] .. offsets[i+1]); valid until the next extraction
+ * call (or precompute / destroy): the match calls only read them, so
+ * several sift_mi_match_pairs_device calls may follow one extraction. */
 int sift_mi_device_results(sift_mi_ctx* ctx, const sift_mi_keypoint** d_kps, const uint8_t** d_desc, size_t* n);
 
 /* Validation read-back (extension, not the crate): the Gaussian planes
@@ -241,6 +243,55 @@ typedef struct {
 int sift_mi_match_descriptors(sift_mi_ctx* ctx, const uint8_t* query, size_t n_query, const uint8_t* train,
                               size_t n_train, int cross_check, sift_mi_match* out, size_t cap, size_t* n_matches);
 
+/* LABELLED EXTENSION (the crate offers only BFMatcher(crossCheck).match):
+ * cv::BFMatcher(NORM_L2).knnMatch(query, train, 2) -- per query its two
+ * nearest train rows, ordered by (integer L2^2, index) ascending (OpenCV's
+ * insertion rule: lowest index first among equals), distance as above.
+ * out[n_query]; where a neighbour is absent (n_train < 2) train_idx is -1 and
+ * distance +INFINITY. */
+typedef struct {
+    int32_t train_idx[2];
+    float distance[2];
+} sift_mi_neighbors;
+int sift_mi_match_neighbors(sift_mi_ctx* ctx, const uint8_t* query, size_t n_query, const uint8_t* train,
+                            size_t n_train, sift_mi_neighbors* out);
+
+/* LABELLED EXTENSION: sift_mi_match_descriptors plus Lowe's ratio test on the
+ * two nearest neighbours: a query is kept only if distance[0] < ratio *
+ * distance[1] (f32, one multiply, strict), and rejected when it has no
+ * second neighbour (n_train < 2).  ratio == 0: no ratio test (the result of
+ * sift_mi_match_descriptors); otherwise 0 < ratio <= 1 (SIFT_MI_EINVAL for a
+ * NaN, a negative value or one above 1).  With cross_check both tests must
+ * pass. */
+int sift_mi_match_ratio(sift_mi_ctx* ctx, const uint8_t* query, size_t n_query, const uint8_t* train,
+                        size_t n_train, float ratio, int cross_check, sift_mi_match* out, size_t cap,
+                        size_t* n_matches);
+
+/* LABELLED EXTENSION: the same for many (query segment, train segment) pairs
+ * of descriptors resident in device memory, in one launch sequence on the
+ * context stream (returns once `out` is written; no allocation once the
+ * context's scratch has grown to the call's size).  d_desc: (n, 128) u8 rows
+ * in device memory, laid out like sift_mi_device_results' descriptors (any
+ * device memory will do, 16-byte aligned); segment s is rows offsets[s] ..
+ * offsets[s+1] (host array of n_segs + 1, e.g. the offsets of
+ * sift_mi_extract_batch_device: one segment per frame).  Pair p matches the
+ * rows of segment pairs[p].query_seg against those of pairs[p].train_seg; its
+ * matches are out[pair_offsets[p] .. pair_offsets[p+1]), in query order, with
+ * segment-relative indices; pairs come in the given order (pair_offsets is a
+ * host array of n_pairs + 1).  An empty segment gives an empty range.  If
+ * cap is too small the call returns SIFT_MI_EINVAL with
+ * pair_offsets[n_pairs] set to the needed count.  SIFT_MI_EINVAL also for a
+ * null argument, a bad ratio (as above), a pair index >= n_segs, decreasing
+ * offsets, and a segment or a sum of segment lengths above 2^31 - 1.
+ * The call only reads d_desc: it never invalidates the context's device
+ * results, so any number of match calls may follow one extraction. */
+typedef struct {
+    uint32_t query_seg, train_seg;
+} sift_mi_seg_pair;
+int sift_mi_match_pairs_device(sift_mi_ctx* ctx, const uint8_t* d_desc, const size_t* offsets, uint32_t n_segs,
+                               const sift_mi_seg_pair* pairs, uint32_t n_pairs, float ratio, int cross_check,
+                               sift_mi_match* out, size_t cap, size_t* pair_offsets);
+
 /* ---- the input step before the path ---------------
  * Baseline (SOF0/SOF1) Huffman JPEG, 1 or 3 components -> 8-bit luma, with
  * the arithmetic of the reference's decode: image 0.25.2 `image::open` /
@@ -300,6 +351,11 @@ typedef struct {
     uint64_t orient_samples;
     uint64_t desc_samples;
     uint64_t pyramid_scan_bytes;
+    /* the segmented matcher (sift_mi_match_pairs_device, sift_mi_match_ratio,
+     * sift_mi_match_neighbors): its kernels' time from HIP events around them
+     * (every call records the two), and the 128 x 128 tiles they covered */
+    double match_ms;
+    uint64_t match_tiles;
 } sift_mi_stats;
 int sift_mi_get_stats(sift_mi_ctx* ctx, sift_mi_stats* out);
 int sift_mi_reset_stats(sift_mi_ctx* ctx);
@@ -309,6 +365,10 @@ int sift_mi_reset_stats(sift_mi_ctx* ctx);
 int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
 
 /* Library version string and last error (thread-local).
+ * 0.5.0: sift_mi_match_neighbors, sift_mi_match_ratio,
+ *        sift_mi_match_pairs_device (2-NN, ratio test, segment pairs of a
+ *        device arena); sift_mi_stats gained match_ms, match_tiles (a larger
+ *        struct); sift_mi_device_results stay valid across match calls.
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

@@ -22,6 +22,7 @@ EXPORTS = [
     "sift_mi_read_batch_scale_space", "sift_mi_batch_octave_dims", "sift_mi_set_path_option",
     "sift_mi_sift_with_precomputed", "sift_mi_compute_descriptor", "sift_mi_gaussian_blur",
     "sift_mi_resize_linear", "sift_mi_resize_nearest", "sift_mi_match_descriptors", "sift_mi_jpeg_dims",
+    "sift_mi_match_neighbors", "sift_mi_match_ratio", "sift_mi_match_pairs_device",
     "sift_mi_decode_jpeg", "sift_mi_decode_jpeg_batch", "sift_mi_get_stats",
     "sift_mi_reset_stats",
     "sift_mi_version", "sift_mi_last_error",
@@ -41,6 +42,16 @@ class Match(ctypes.Structure):
     _fields_ = [("query_idx", ctypes.c_int32), ("train_idx", ctypes.c_int32), ("distance", ctypes.c_float)]
 
 
+class Neighbors(ctypes.Structure):
+    """include/sift_mi.h sift_mi_neighbors (knnMatch, k = 2; -1 / +inf where absent)."""
+    _fields_ = [("train_idx", ctypes.c_int32 * 2), ("distance", ctypes.c_float * 2)]
+
+
+class SegPair(ctypes.Structure):
+    """include/sift_mi.h sift_mi_seg_pair."""
+    _fields_ = [("query_seg", ctypes.c_uint32), ("train_seg", ctypes.c_uint32)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("pyramid_ms", ctypes.c_double), ("detect_ms", ctypes.c_double),
                 ("orient_ms", ctypes.c_double), ("order_ms", ctypes.c_double),
@@ -49,7 +60,8 @@ class Stats(ctypes.Structure):
                 ("frames", ctypes.c_uint64), ("extrema", ctypes.c_uint64),
                 ("keypoints", ctypes.c_uint64), ("band_reruns", ctypes.c_uint64),
                 ("stage_reruns", ctypes.c_uint64), ("orient_samples", ctypes.c_uint64),
-                ("desc_samples", ctypes.c_uint64), ("pyramid_scan_bytes", ctypes.c_uint64)]
+                ("desc_samples", ctypes.c_uint64), ("pyramid_scan_bytes", ctypes.c_uint64),
+                ("match_ms", ctypes.c_double), ("match_tiles", ctypes.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -107,6 +119,9 @@ def lib():
         "sift_mi_resize_linear": [vp, vp, u32, u32, u32, u32, vp],
         "sift_mi_resize_nearest": [vp, vp, u32, u32, u32, u32, vp],
         "sift_mi_match_descriptors": [vp, vp, sz, vp, sz, i32, vp, sz, P(sz)],
+        "sift_mi_match_neighbors": [vp, vp, sz, vp, sz, vp],
+        "sift_mi_match_ratio": [vp, vp, sz, vp, sz, f32, i32, vp, sz, P(sz)],
+        "sift_mi_match_pairs_device": [vp, vp, P(sz), u32, vp, u32, f32, i32, vp, sz, P(sz)],
         "sift_mi_jpeg_dims": [vp, sz, P(u32), P(u32)],
         "sift_mi_decode_jpeg": [vp, vp, sz, vp, sz, i32],
         "sift_mi_decode_jpeg_batch": [vp, P(vp), P(sz), u32, vp, sz, sz, i32],

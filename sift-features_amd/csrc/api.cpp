@@ -149,11 +149,179 @@ int jpeg_guard(F&& body) {
         return rc;
     }
 }
+// No C++ exception leaves the match entry points (their host tables are
+// sized by the caller's pair count).
+template <class F>
+int match_guard(F&& body) {
+    int rc = SIFT_MI_EINVAL;
+    const char* what = "match: exception";
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        rc = SIFT_MI_ENOMEM;
+        what = "match: host allocation failed";
+    } catch (...) {
+    }
+    try {
+        return fail(rc, what);
+    } catch (...) {
+        return rc;
+    }
+}
+
+// Grow-only pooled buffers of the matcher: half again on growth, so a
+// sequence of slightly larger calls does not reallocate every time.
+template <class B>
+int pool(B& b, size_t n) {
+    if (n <= b.cap && b.p) return 0;
+    return b.ensure(std::max(n, b.cap + b.cap / 2));
+}
+
+int check_ratio(float ratio) {
+    if (!(ratio >= 0.0f && ratio <= 1.0f)) return fail(SIFT_MI_EINVAL, "ratio must be 0 (no ratio test) or in (0, 1]");
+    return 0;
+}
+
+// The segmented matcher on device rows d_desc: validates the segments and
+// pairs, runs the launch sequence on the context stream and leaves, per
+// (pair, query) slot in pair order, the kept train index (-1: no match) and
+// distance in c->match.h_tix / h_dist (with `neighbors`, both neighbours in
+// h_nb_idx / h_nb_dist), synchronised.  P[p].qoff = pair p's first slot.
+int match_pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets, uint32_t n_segs,
+                    const sift_mi_seg_pair* pairs, uint32_t n_pairs, float ratio, int cross_check, bool neighbors,
+                    std::vector<MatchPair>& P) {
+    constexpr size_t kMax = 0x7fffffff;
+    if (((uintptr_t)d_desc & 15) != 0) return fail(SIFT_MI_EINVAL, "d_desc must be 16-byte aligned");
+    for (uint32_t s = 0; s < n_segs; s++) {
+        if (offsets[s + 1] < offsets[s]) return fail(SIFT_MI_EINVAL, "offsets decrease");
+        if (offsets[s + 1] - offsets[s] > kMax) return fail(SIFT_MI_EINVAL, "segment longer than 2^31 - 1 rows");
+    }
+    const size_t row_base = offsets[0], n_rows = offsets[n_segs] - offsets[0];
+    if (n_rows > kMax) return fail(SIFT_MI_EINVAL, "segments sum to more than 2^31 - 1 rows");
+    P.assign((size_t)n_pairs + 1, MatchPair{});
+    std::vector<char> used(n_segs, 0);
+    size_t slots = 0, cols = 0, tiles = 0;
+    for (uint32_t p = 0; p < n_pairs; p++) {
+        const uint32_t qs = pairs[p].query_seg, ts = pairs[p].train_seg;
+        if (qs >= n_segs || ts >= n_segs) return fail(SIFT_MI_EINVAL, "pair names a segment >= n_segs");
+        MatchPair& m = P[p];
+        m.qrow0 = (uint32_t)(offsets[qs] - row_base);
+        m.nq = (uint32_t)(offsets[qs + 1] - offsets[qs]);
+        m.trow0 = (uint32_t)(offsets[ts] - row_base);
+        m.nt = (uint32_t)(offsets[ts + 1] - offsets[ts]);
+        m.qoff = (uint32_t)slots;
+        m.toff = (uint32_t)cols;
+        m.tile0 = (uint32_t)tiles;
+        slots += m.nq;
+        cols += m.nt;
+        if (m.nq && m.nt) {
+            tiles += (size_t)((m.nq + 127) / 128) * ((m.nt + 127) / 128);
+            used[qs] = used[ts] = 1;
+        }
+        if (slots > kMax || cols > kMax || tiles > kMax)
+            return fail(SIFT_MI_EINVAL, "pairs sum to more than 2^31 - 1 queries, train rows or tiles");
+    }
+    P[n_pairs].qoff = (uint32_t)slots;
+    P[n_pairs].toff = (uint32_t)cols;
+    P[n_pairs].tile0 = (uint32_t)tiles;
+    if (slots == 0) return 0;
+
+    CHK(set_device(c));
+    MatchScratch& M = c->match;
+    // table: the pairs, then the 256-row blocks of the segments in use (their norms)
+    const size_t pair_words = P.size() * (sizeof(MatchPair) / 4);
+    size_t n_blocks = 0;
+    for (uint32_t s = 0; s < n_segs; s++)
+        if (used[s]) n_blocks += (offsets[s + 1] - offsets[s] + 255) / 256;
+    const size_t words = pair_words + 2 * n_blocks;
+    CHK(pool(M.h_table, words));
+    std::memcpy(M.h_table.p, P.data(), pair_words * 4);
+    uint32_t* blk = M.h_table.p + pair_words;
+    for (uint32_t s = 0; s < n_segs; s++) {
+        if (!used[s]) continue;
+        for (size_t r = offsets[s]; r < offsets[s + 1]; r += 256) {
+            *blk++ = (uint32_t)(r - row_base);
+            *blk++ = (uint32_t)std::min<size_t>(256, offsets[s + 1] - r);
+        }
+    }
+    CHK(pool(M.table, words));
+    CHK(pool(M.nrm, n_rows));
+    CHK(pool(M.best, slots));
+    CHK(pool(M.second, slots));
+    CHK(pool(M.col, cols));
+    CHK(pool(M.tix, slots));
+    CHK(pool(M.dist, slots));
+    CHK(pool(M.h_tix, slots));
+    CHK(pool(M.h_dist, slots));
+    if (neighbors) {
+        CHK(pool(M.nb_idx, 2 * slots));
+        CHK(pool(M.nb_dist, 2 * slots));
+        CHK(pool(M.h_nb_idx, 2 * slots));
+        CHK(pool(M.h_nb_dist, 2 * slots));
+    }
+    if (!M.t0) HIPCHK(hipEventCreate(&M.t0));
+    if (!M.t1) HIPCHK(hipEventCreate(&M.t1));
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemcpyAsync(M.table.p, M.h_table.p, words * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(M.t0, st));
+    launch_match_pairs(d_desc + row_base * kDescSize, reinterpret_cast<const MatchPair*>(M.table.p), (int)n_pairs,
+                       (uint32_t)tiles, (uint32_t)slots, (uint32_t)cols,
+                       reinterpret_cast<const uint2*>(M.table.p + pair_words), (uint32_t)n_blocks, cross_check ? 1 : 0,
+                       ratio, M.nrm.p, M.best.p, M.second.p, M.col.p, M.tix.p, M.dist.p,
+                       neighbors ? M.nb_idx.p : nullptr, neighbors ? M.nb_dist.p : nullptr, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(M.t1, st));
+    HIPCHK(hipMemcpyAsync(M.h_tix.p, M.tix.p, slots * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(M.h_dist.p, M.dist.p, slots * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (neighbors) {
+        HIPCHK(hipMemcpyAsync(M.h_nb_idx.p, M.nb_idx.p, 2 * slots * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(M.h_nb_dist.p, M.nb_dist.p, 2 * slots * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, M.t0, M.t1) == hipSuccess) c->stats.match_ms += ms;
+    c->stats.match_tiles += tiles;
+    return 0;
+}
+
+// The kept slots of match_pairs_run as sift_mi_match rows, pair after pair.
+int match_pairs_collect(const sift_mi_ctx* c, const std::vector<MatchPair>& P, sift_mi_match* out, size_t cap,
+                        size_t* pair_offsets) {
+    const size_t n_pairs = P.size() - 1, slots = P[n_pairs].qoff;
+    const int* tix = c->match.h_tix.p;
+    const float* dist = c->match.h_dist.p;
+    size_t n = 0;
+    for (size_t i = 0; i < slots; i++) n += tix[i] >= 0;
+    if (cap < n || (n && !out)) {
+        pair_offsets[n_pairs] = n;
+        return fail(SIFT_MI_EINVAL, "cap < number of matches (pair_offsets[n_pairs])");
+    }
+    size_t k = 0;
+    for (size_t p = 0; p < n_pairs; p++) {
+        pair_offsets[p] = k;
+        for (uint32_t i = 0; i < P[p].nq; i++) {
+            const size_t s = (size_t)P[p].qoff + i;
+            if (tix[s] >= 0) out[k++] = sift_mi_match{(int32_t)i, tix[s], dist[s]};
+        }
+    }
+    pair_offsets[n_pairs] = k;
+    return 0;
+}
+
+// Host descriptor arrays as the two segments of the context's own arena.
+int match_upload(sift_mi_ctx* c, const uint8_t* query, size_t nq, const uint8_t* train, size_t nt) {
+    CHK(set_device(c));
+    MatchScratch& M = c->match;
+    CHK(pool(M.desc, (nq + nt) * kDescSize));
+    if (nq) HIPCHK(hipMemcpyAsync(M.desc.p, query, nq * kDescSize, hipMemcpyHostToDevice, c->stream));
+    if (nt) HIPCHK(hipMemcpyAsync(M.desc.p + nq * kDescSize, train, nt * kDescSize, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
 }  // namespace
 
 extern "C" {
 
-const char* sift_mi_version(void) { return "sift_mi 0.4.0 (gfx950)"; }
+const char* sift_mi_version(void) { return "sift_mi 0.5.0 (gfx950)"; }
 const char* sift_mi_last_error(void) { return g_err.c_str(); }
 
 int sift_mi_create(int device_ordinal, sift_mi_profile profile, sift_mi_ctx** out) {
@@ -557,6 +725,60 @@ int sift_mi_match_descriptors(sift_mi_ctx* c, const uint8_t* query, size_t nq, c
     for (size_t i = 0; i < nq; i++)
         if (h_t[i] >= 0) out[k++] = sift_mi_match{(int32_t)i, h_t[i], h_d[i]};
     return 0;
+}
+
+// ---- 2-NN, ratio test, segment pairs (labelled extensions; match.hip) --------
+int sift_mi_match_pairs_device(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets, uint32_t n_segs,
+                               const sift_mi_seg_pair* pairs, uint32_t n_pairs, float ratio, int cross_check,
+                               sift_mi_match* out, size_t cap, size_t* pair_offsets) {
+    if (!c || !d_desc || !offsets || !pairs || !pair_offsets) return fail(SIFT_MI_EINVAL, "null argument");
+    CHK(check_ratio(ratio));
+    return match_guard([&]() -> int {
+        std::vector<MatchPair> P;
+        CHK(match_pairs_run(c, d_desc, offsets, n_segs, pairs, n_pairs, ratio, cross_check, false, P));
+        return match_pairs_collect(c, P, out, cap, pair_offsets);
+    });
+}
+
+int sift_mi_match_ratio(sift_mi_ctx* c, const uint8_t* query, size_t nq, const uint8_t* train, size_t nt,
+                        float ratio, int cross_check, sift_mi_match* out, size_t cap, size_t* n_matches) {
+    if (!c || !n_matches || (nq && !query) || (nt && !train)) return fail(SIFT_MI_EINVAL, "bad arguments");
+    CHK(check_ratio(ratio));
+    if (nq > 0x7fffffff || nt > 0x7fffffff || nq + nt > 0x7fffffff)
+        return fail(SIFT_MI_EINVAL, "descriptor set too large");
+    *n_matches = 0;
+    if (nq == 0) return 0;
+    return match_guard([&]() -> int {
+        CHK(match_upload(c, query, nq, train, nt));
+        const size_t offsets[3] = {0, nq, nq + nt};
+        const sift_mi_seg_pair pair{0, 1};
+        std::vector<MatchPair> P;
+        CHK(match_pairs_run(c, c->match.desc.p, offsets, 2, &pair, 1, ratio, cross_check, false, P));
+        size_t po[2] = {0, 0};
+        const int rc = match_pairs_collect(c, P, out, cap, po);
+        *n_matches = po[1];
+        return rc;
+    });
+}
+
+int sift_mi_match_neighbors(sift_mi_ctx* c, const uint8_t* query, size_t nq, const uint8_t* train, size_t nt,
+                            sift_mi_neighbors* out) {
+    if (!c || (nq && (!query || !out)) || (nt && !train)) return fail(SIFT_MI_EINVAL, "bad arguments");
+    if (nq > 0x7fffffff || nt > 0x7fffffff || nq + nt > 0x7fffffff)
+        return fail(SIFT_MI_EINVAL, "descriptor set too large");
+    if (nq == 0) return 0;
+    return match_guard([&]() -> int {
+        CHK(match_upload(c, query, nq, train, nt));
+        const size_t offsets[3] = {0, nq, nq + nt};
+        const sift_mi_seg_pair pair{0, 1};
+        std::vector<MatchPair> P;
+        CHK(match_pairs_run(c, c->match.desc.p, offsets, 2, &pair, 1, 0.0f, 0, true, P));
+        const int* idx = c->match.h_nb_idx.p;
+        const float* dist = c->match.h_nb_dist.p;
+        for (size_t i = 0; i < nq; i++)
+            out[i] = sift_mi_neighbors{{idx[2 * i], idx[2 * i + 1]}, {dist[2 * i], dist[2 * i + 1]}};
+        return 0;
+    });
 }
 
 int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height) {

@@ -267,6 +267,26 @@ struct Slot {
     CounterLayout layout() const { return CounterLayout{m}; }
 };
 
+// Pooled scratch of the segmented matcher (sift_mi_match_pairs_device and the
+// host-array calls over it): grows on demand, freed with the context.
+struct MatchScratch {
+    DevBuf<uint8_t> desc;      // host-array calls: [query rows | train rows]
+    DevBuf<uint32_t> table;    // MatchPair[n_pairs + 1] | norm blocks (uint2)
+    PinBuf<uint32_t> h_table;
+    DevBuf<int> nrm;           // per arena row: |row|^2 - 256 sum(row)
+    DevBuf<unsigned long long> best, second;  // per (pair, query)
+    DevBuf<unsigned long long> col;           // per (pair, train)
+    DevBuf<int> tix, nb_idx;
+    DevBuf<float> dist, nb_dist;
+    PinBuf<int> h_tix, h_nb_idx;
+    PinBuf<float> h_dist, h_nb_dist;
+    hipEvent_t t0 = nullptr, t1 = nullptr;  // around the kernels (sift_mi_stats.match_ms)
+    ~MatchScratch() {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+    }
+};
+
 }  // namespace siftmi
 
 struct sift_mi_ctx {
@@ -337,6 +357,7 @@ struct sift_mi_ctx {
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
     uint32_t batch_frames = 0;
+    siftmi::MatchScratch match;
     sift_mi_stats stats{};
 };
 

@@ -301,6 +301,23 @@ void launch_match(const uint8_t* q, int nq, const uint8_t* t, int nt, int cross_
                   unsigned long long* row_best, unsigned long long* col_best, int* train_idx, float* dist,
                   hipStream_t st);
 
+// Segmented 2-NN matching of (query segment, train segment) pairs of one
+// descriptor arena.  pairs[n_pairs + 1] (the last entry closes the prefixes):
+// the segments' first arena rows and lengths, the pair's first slot in the
+// per-(pair, query) arrays (best / second / outputs) and in the per-(pair,
+// train) col_best, and its first 128 x 128 tile of the 1-D grid.
+struct MatchPair {
+    uint32_t qrow0, nq, trow0, nt, qoff, toff, tile0, pad;
+};
+// norm_blocks[b] = (first arena row, rows <= 256) of the segments in use; nrm
+// is indexed by arena row.  nb_idx / nb_dist (2 per slot) may be null.
+// ratio == 0: no ratio test.
+void launch_match_pairs(const uint8_t* d, const MatchPair* pairs, int n_pairs, uint32_t n_tiles, uint32_t n_slots,
+                        uint32_t n_cols, const uint2* norm_blocks, uint32_t n_norm_blocks, int cross_check,
+                        float ratio, int* nrm, unsigned long long* best, unsigned long long* second,
+                        unsigned long long* col_best, int* train_idx, float* dist, int* nb_idx, float* nb_dist,
+                        hipStream_t st);
+
 // describe.hip
 // Descriptor work queues: keypoint i belongs to queue i % kDescQueues, which
 // hands out its keypoints in order; 8 counters on separate 128-B lines (one

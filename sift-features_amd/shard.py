@@ -132,7 +132,8 @@ def device_results(ctx, device=None):
     context's GPU over the results of its last sift_batch_device(...,
     fetch=False) call -- every frame's keypoints and descriptors in frame
     order (sift_mi_device_results), wrapped without a copy; valid until the
-    context's next call."""
+    context's next extraction call (match_frames / match_pairs_device only
+    read them)."""
     import torch
     kp, desc, n = ctx.device_results()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

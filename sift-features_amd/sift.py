@@ -107,6 +107,12 @@ def _f32_image(img):
     return a
 
 
+def _match_arrays(a, lo, hi):
+    """Rows lo..hi of a sift_mi_match record array as (query_idx, train_idx, distance)."""
+    a = a[lo:hi]
+    return (a["query_idx"].astype(np.int32), a["train_idx"].astype(np.int32), a["distance"].astype(np.float32))
+
+
 def _limit(features_limit):
     if features_limit is None:
         return -1
@@ -245,7 +251,8 @@ class Context:
     def device_results(self):
         """(keypoints device pointer, descriptors device pointer, n) of the last
         sift_batch_device(..., fetch=False): every frame's results, concatenated
-        in frame order, in HBM."""
+        in frame order, in HBM.  Valid until the next extraction call; the
+        match calls only read them."""
         kp, desc, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
         check(lib().sift_mi_device_results(self._h, ctypes.byref(kp), ctypes.byref(desc), ctypes.byref(n)))
         return kp.value, desc.value, n.value
@@ -322,19 +329,65 @@ class Context:
         return out
 
     # -- matching (examples/sift-match.rs:30-35) -----------------------------
-    def match_descriptors(self, query, train, cross_check=True):
+    def match_descriptors(self, query, train, cross_check=True, ratio=None):
         """cv::BFMatcher(NORM_L2, crossCheck).match(query, train) on the GPU.
         query / train: (n, 128) u8 descriptors.  Returns (query_idx, train_idx,
-        distance) arrays in query order."""
+        distance) arrays in query order.  LABELLED EXTENSION: with `ratio`
+        (0 < ratio <= 1) a query is kept only if its nearest distance is below
+        ratio * its second nearest (Lowe's ratio test; sift_mi_match_ratio)."""
         q = np.ascontiguousarray(query, dtype=np.uint8).reshape(-1, DESCRIPTOR_SIZE)
         t = np.ascontiguousarray(train, dtype=np.uint8).reshape(-1, DESCRIPTOR_SIZE)
         out = (_lib.Match * max(len(q), 1))()
         n = ctypes.c_size_t()
-        check(lib().sift_mi_match_descriptors(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t),
-                                              1 if cross_check else 0, out, len(q), ctypes.byref(n)))
-        a = np.ctypeslib.as_array(out)[: n.value]
-        return (a["query_idx"].astype(np.int32), a["train_idx"].astype(np.int32),
-                a["distance"].astype(np.float32))
+        if ratio is None:
+            check(lib().sift_mi_match_descriptors(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t),
+                                                  1 if cross_check else 0, out, len(q), ctypes.byref(n)))
+        else:
+            check(lib().sift_mi_match_ratio(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t), float(ratio),
+                                            1 if cross_check else 0, out, len(q), ctypes.byref(n)))
+        return _match_arrays(np.ctypeslib.as_array(out), 0, n.value)
+
+    def match_neighbors(self, query, train):
+        """LABELLED EXTENSION: cv::BFMatcher(NORM_L2).knnMatch(query, train, 2).
+        Returns (idx (n, 2) int32, dist (n, 2) f32): each query's two nearest
+        train rows by (distance, index); -1 / inf where train has fewer rows."""
+        q = np.ascontiguousarray(query, dtype=np.uint8).reshape(-1, DESCRIPTOR_SIZE)
+        t = np.ascontiguousarray(train, dtype=np.uint8).reshape(-1, DESCRIPTOR_SIZE)
+        out = (_lib.Neighbors * max(len(q), 1))()
+        check(lib().sift_mi_match_neighbors(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t), out))
+        a = np.ctypeslib.as_array(out)[: len(q)]
+        return a["train_idx"].astype(np.int32).reshape(-1, 2), a["distance"].astype(np.float32).reshape(-1, 2)
+
+    def match_pairs_device(self, d_desc_ptr, offsets, pairs, ratio=None, cross_check=True):
+        """Match (query segment, train segment) pairs of device-resident
+        descriptors in one launch sequence (sift_mi_match_pairs_device).
+        d_desc_ptr: device pointer of (n, 128) u8 rows; segment s is rows
+        offsets[s]..offsets[s+1]; pairs: (query_seg, train_seg) tuples.
+        Returns one (query_idx, train_idx, distance) triple per pair, indices
+        relative to the pair's segments."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
+            raise ValueError("offsets: n_segs + 1 non-negative row numbers")
+        c_offs = (ctypes.c_size_t * len(offs))(*[int(v) for v in offs])
+        pr = [(int(a), int(b)) for a, b in pairs]
+        c_pairs = (_lib.SegPair * max(len(pr), 1))(*[_lib.SegPair(a, b) for a, b in pr])
+        n_seg = len(offs) - 1
+        cap = sum(int(offs[a + 1] - offs[a]) for a, _ in pr if 0 <= a < n_seg and offs[a + 1] >= offs[a])
+        out = (_lib.Match * max(cap, 1))()
+        po = (ctypes.c_size_t * (len(pr) + 1))()
+        check(lib().sift_mi_match_pairs_device(self._h, ctypes.c_void_p(d_desc_ptr), c_offs, n_seg, c_pairs, len(pr),
+                                               float(ratio or 0.0), 1 if cross_check else 0, out, cap, po))
+        a = np.ctypeslib.as_array(out)
+        return [_match_arrays(a, po[p], po[p + 1]) for p in range(len(pr))]
+
+    def match_frames(self, offsets, pairs, ratio=None, cross_check=True):
+        """match_pairs_device on the descriptors the last
+        sift_batch_device(..., fetch=False) left in HBM: `offsets` as that
+        call returned them, `pairs` of (query frame, train frame)."""
+        _, d_desc, n = self.device_results()
+        if int(offsets[-1]) > n:
+            raise ValueError("offsets reach beyond the device results")
+        return self.match_pairs_device(d_desc, offsets, pairs, ratio, cross_check)
 
     # -- the input step (SURVEY.md 8(f) row 2) ------------------------------
     def decode_jpeg(self, data):
@@ -515,9 +568,26 @@ def decode_jpeg(data):
     return default_context().decode_jpeg(data)
 
 
-def match_descriptors(query, train, cross_check=True):
-    """examples/sift-match.rs:30-35: BFMatcher(NORM_L2, crossCheck).match."""
-    return default_context().match_descriptors(query, train, cross_check)
+def match_descriptors(query, train, cross_check=True, ratio=None):
+    """examples/sift-match.rs:30-35: BFMatcher(NORM_L2, crossCheck).match
+    (`ratio`: Lowe's ratio test, a labelled extension)."""
+    return default_context().match_descriptors(query, train, cross_check, ratio)
+
+
+def match_neighbors(query, train):
+    """LABELLED EXTENSION: BFMatcher(NORM_L2).knnMatch(query, train, 2)."""
+    return default_context().match_neighbors(query, train)
+
+
+def match_pairs_device(d_desc_ptr, offsets, pairs, ratio=None, cross_check=True):
+    """Context.match_pairs_device on the default context."""
+    return default_context().match_pairs_device(d_desc_ptr, offsets, pairs, ratio, cross_check)
+
+
+def match_frames(offsets, pairs, ratio=None, cross_check=True):
+    """Context.match_frames on the default context (its last
+    sift_batch_device(..., fetch=False) results)."""
+    return default_context().match_frames(offsets, pairs, ratio, cross_check)
 
 
 def stable_sort_xy_size(keypoints_array):

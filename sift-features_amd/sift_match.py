@@ -1,0 +1,53 @@
+"""sift-match: the counterpart of the crate's examples/sift-match.rs on the
+MI355X path.
+
+    python sift-features_amd/sift_match.py <a.jpg> <b.jpg> [--ratio R] [--processing opencv|imageproc] [--device N]
+
+examples/sift-match.rs:30-35, :87-97 opens two images, runs `sift()` on each and
+matches the second's descriptors (query) against the first's (train) with
+cv::BFMatcher(NORM_L2, crossCheck = true); it then draws the matches, which
+this counterpart does not.  Here both JPEGs are decoded by the context's
+decoder (jpeg.hip), `sift()` runs on the GPU through the C ABI and the
+matcher is the MFMA kernel of match.hip.  Prints both keypoint counts and the
+number of cross-checked matches.  `--ratio R` (0 < R <= 1) adds Lowe's ratio
+test on the two nearest neighbours, a labelled extension (the crate has
+none).  Exits non-zero (with the library's error) when the HIP library or
+the device is missing: there is no CPU fallback.
+"""
+import argparse
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="sift-match", description=__doc__.split("\n\n")[0])
+    ap.add_argument("path_a")
+    ap.add_argument("path_b")
+    ap.add_argument("--ratio", type=float, default=None)
+    ap.add_argument("--processing", choices=("imageproc", "opencv"), default="imageproc")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    import pkg_loader
+    pkg = pkg_loader.load()
+    proc = pkg.ImageprocProcessing if a.processing == "imageproc" else pkg.OpenCVProcessing
+    datas = []
+    for path in (a.path_a, a.path_b):
+        with open(path, "rb") as f:
+            datas.append(f.read())
+    ctx = pkg.Context(a.device, proc)
+    try:
+        res_a, res_b = (ctx.sift_jpeg(d) for d in datas)
+        qi, ti, dist = ctx.match_descriptors(res_b.descriptors, res_a.descriptors, cross_check=True, ratio=a.ratio)
+    finally:
+        ctx.close()
+    print(f"{len(res_a)} keypoints")
+    print(f"{len(res_b)} keypoints")
+    print(f"{len(qi)} matches" + (f" (ratio {a.ratio:g})" if a.ratio is not None else ""))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
