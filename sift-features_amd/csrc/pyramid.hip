@@ -669,15 +669,23 @@ __global__ __launch_bounds__(256, (strip_minb<R, NXT>())) void k_blur_strip(
 //
 // A strip owns the 112 output columns [X, X + 112).  Blur A (radius Ra) is
 // the strip scheme above with its 128 columns starting at X - 8: its column
-// pass writes G_s rows into a ring of three LDS slots laid out as blur B's
+// pass writes G_s rows into a ring of two LDS slots laid out as blur B's
 // (radius Rb) input window [X - 8, X + 136), so B's row pass is the same
 // 16-item lane map (its last 16 outputs read junk and are dropped) and B's
 // column pass stores lanes 0..55.  Vertically B lags A by two chunks:
-//   step k:  P1  store A-input chunk k + 1 (prefetched), prefetch k + 2
+//   step k:  P1  store A-input chunk k + 1 (prefetched), prefetch k + 2 |
+//                G_s chunk k - 1 (registers, from P3 of step k - 1) -> slot
+//                (k - 1) % 2
 //            P2  row pass A on chunk k + 1 | row pass B on G_s chunk k - 1
-//            P3  column pass A -> G_s chunk k (slot k % 3, HBM rows of this
-//                segment) | column pass B -> G_{s+1} rows of chunk k - 2
-// (one phase's two halves touch disjoint slots).
+//            P3  column pass A -> G_s chunk k (HBM rows of this segment; the
+//                wave's 4 rows stay in registers) | column pass B ->
+//                G_{s+1} rows of chunk k - 2 (slots k % 2, (k - 1) % 2)
+// (one phase's two halves touch disjoint slots).  G_s chunk k shares its
+// slot with chunk k - 2, which column pass B still reads in P3 of step k:
+// so A's rows wait in registers (VB f2v per lane) and land in P1 of step
+// k + 1, after the barrier that ends those reads and two barriers before
+// their first reader (fixup / row pass B in P2 of step k + 1).  Two slots
+// instead of three: four workgroups per CU fit the LDS.
 //
 // Exactness at the image borders: G_s rows above / below the image come out
 // of A's column pass as the reflect-101 images of real rows bit for bit (the
@@ -693,9 +701,9 @@ struct PairGeom {
     static constexpr int HB = GB::HWL;             // G_s halo columns of B's window
     static constexpr int TWO = GA::TW - 2 * HB;   // output columns per strip
     static constexpr int NBW = GB::NCW;           // G_s chunks in a column-pass window of B
-    // B ring: the two-chunk window + the chunk being written (the two column
-    // passes share a phase)
-    static constexpr int NBR = NBW + 1;
+    // B ring: the two-chunk window; the chunk column pass A produces while
+    // column pass B reads the window waits in registers (blur2_body)
+    static constexpr int NBR = NBW;
     static constexpr int LDS_FLOATS = 2 * GA::SLOT + NBR * GB::SLOT;
     static constexpr int MINB = 163840 / (4 * LDS_FLOATS + 2048) < 4 ? 163840 / (4 * LDS_FLOATS + 2048) : 4;
     static_assert(GA::HWL <= 8 && GA::NCW == 2, "A: radius <= 8");
@@ -704,11 +712,12 @@ struct PairGeom {
 };
 
 // A's column pass for wave WV: G_s rows y0 .. y0 + VB - 1 (y0 = first row of
-// the chunk + WV*VB) of columns xa + 2*lane into B's slot, and into HBM for
-// the rows [gys, gye) and columns [X, min(X + TWO, W)) this strip owns (NXT:
-// with the next octave's base, nearest 1/2 = pixel (2x, 2y)).
+// the chunk + WV*VB) of columns xa + 2*lane into `keep` (B's slot rows
+// WV*VB .. + VB - 1, written by blur2_body in the next step's P1), and into
+// HBM for the rows [gys, gye) and columns [X, min(X + TWO, W)) this strip owns
+// (NXT: with the next octave's base, nearest 1/2 = pixel (2x, 2y)).
 template <class GA, int WV, bool NXT, int P = kProfileOpenCV>
-__device__ __forceinline__ void pair_colpass_a(const float* sa, const float* sb, float* bslot, int bip,
+__device__ __forceinline__ void pair_colpass_a(const float* sa, const float* sb, f2v (&keep)[GA::VB],
                                                const BlurTaps& taps, int lane, int y, int gys, int gye, int xa,
                                                int hb, int W, int pitch, int two, __amdgpu_buffer_rsrc_t rd,
                                                __amdgpu_buffer_rsrc_t rn, int pitch_n, int wn, int hn) {
@@ -747,7 +756,7 @@ __device__ __forceinline__ void pair_colpass_a(const float* sa, const float* sb,
                 acc = acc + v[o + t] * kt;
             }
         }
-        *(f2v*)(bslot + (WV * GA::VB + o) * bip + 2 * lane) = acc;
+        keep[o] = acc;
         // predicated by out-of-range offsets, a static store count (see strip_colpass)
         const int gy = y0 + o;
         const uint32_t rowbad = gy >= gys && gy < gye ? 0u : kStoreDrop;  // uniform
@@ -848,13 +857,22 @@ __device__ __forceinline__ void blur2_body(AIn& ain, float* lds, __amdgpu_buffer
     const int nout = (ye - ys + S - 1) / S;
     const int ng = nout + NBW - 2, na = ng + 1;
     const int ga = ys - Rb - Ra - LOFF;  // first A-input row (chunk 0)
+    // column pass A's rows of G_s chunk k (this wave's VB, this lane's column
+    // pair) from P3 of step k to P1 of step k + 1
+    f2v keep[GA::VB] = {};
+    float* const kdst = bslot + (wv * GA::VB) * GB::IWP + 2 * lane;
     ain.prefetch(ga);
     ain.store(aslot, ga);
     ain.prefetch(ga + S);
     __syncthreads();
     strip_rowpass<GA, P>(aslot, taps_a, prow, pq);
     for (int k = 0; k <= nout + NBW - 1; k++) {
-        __syncthreads();  // P1
+        __syncthreads();  // P1: column pass B of step k - 1 is done with slot (k - 1) % NBR
+        if (k >= 1) {  // chunk k - 1 <= ng: read by row pass B below and column pass B of steps k, k + 1
+#pragma unroll
+            for (int o = 0; o < GA::VB; o++)
+                *(f2v*)(kdst + ((k - 1) % NBR) * GB::SLOT + o * GB::IWP) = keep[o];
+        }
         if (k + 1 <= na) {
             ain.store(aslot + ((k + 1) & 1) * GA::SLOT, ga + (k + 1) * S);
             if (k + 2 <= na) ain.prefetch(ga + (k + 2) * S);
@@ -903,13 +921,12 @@ __device__ __forceinline__ void blur2_body(AIn& ain, float* lds, __amdgpu_buffer
         if (k <= ng) {
             const float* s0 = aslot + (k & 1) * GA::SLOT;
             const float* s1 = aslot + ((k + 1) & 1) * GA::SLOT;
-            float* dstb = bslot + (k % NBR) * GB::SLOT;
             const int y = ys - Rb - LOFF + k * S;  // first G_s row of chunk k
             switch (wv) {
 #define COLA(w)                                                                                                       \
     case w:                                                                                                           \
-        pair_colpass_a<GA, w, NXT, P>(s0, s1, dstb, GB::IWP, taps_a, lane, y, ys, ye, xa, Q::HB, W, pitch, Q::TWO, ra,\
-                                   rn, pitch_n, wn, hn);                                                              \
+        pair_colpass_a<GA, w, NXT, P>(s0, s1, keep, taps_a, lane, y, ys, ye, xa, Q::HB, W, pitch, Q::TWO, ra, rn,    \
+                                      pitch_n, wn, hn);                                                               \
         break;
                 COLA(0) COLA(1) COLA(2) COLA(3)
                 default:

@@ -529,10 +529,22 @@ __device__ __forceinline__ ScanMasks extremum3_masks(const float (&prv)[kDogPerO
     return ScanMasks{ok[0], ok[1], ok[2]};
 }
 
+// Three waves per SIMD: 168 VGPRs.  The live set, per lane: the column
+// window win[2R + 1] (54 at R = 13), three RowBufs (36), the rolling DoG rows
+// of both halves (20), the row pass's taps in flight (2 batches of BD2_TAPS
+// pairs: 16) and about 30 of addresses and masks -- 162 VGPRs (OpenCV) / 168
+// (imageproc), no scratch.  Forcing the cap on the earlier form (all 2R + 1
+// taps read before the chain, four RowBufs: 208 VGPRs) spilled 196 B.
 #ifndef SIFT_BD2_WPE
-#define SIFT_BD2_WPE 1
+#define SIFT_BD2_WPE 3
 #endif
-template <int R, int P, int NB, int U>
+// ring taps per read batch of the row pass: at 6 the imageproc instance
+// (unfused chain: a product per tap beside the sum) spills 40 B, at 4 neither
+// does; the whole bench is the same at either
+#ifndef BD2_TAPS
+#define BD2_TAPS 4
+#endif
+template <int R, int P>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_BD2_WPE))) void k_blur_detect_pair(
     const BlurDetectLaunch L) {
     static_assert(R <= 13 && R + 3 <= BD_RING, "ring geometry");
@@ -587,17 +599,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_BD2_WP
         // row filter of G_4 row q at this lane's two columns
         auto rowpass = [&](int q) -> bd_f2 {
             const bd_f2* p = rg + (q & (BD_RING - 1)) * BD2_SLOTS + lane;
-            bd_f2 v[2 * R + 1];
+            // The chain runs from tap 0, so the taps stream through in
+            // batches of BD2_TAPS: one batch's reads are in flight while the
+            // chain consumes the batch before (2 BD2_TAPS register pairs live
+            // instead of 2R + 1).  The empty asm after a batch takes the
+            // chain's value and orders memory: the reads of the batch after
+            // next cannot be issued before this batch is consumed
+            constexpr int NT = 2 * R + 1;
+            bd_f2 v[NT];
 #pragma unroll
-            for (int t = 0; t <= 2 * R; t++) v[t] = p[t];
-            bd_f2 acc = v[0] * L.taps.k[R];
+            for (int t = 0; t < BD2_TAPS && t < NT; t++) v[t] = p[t];
+            bd_f2 acc = bd_f2{0.0f, 0.0f};
 #pragma unroll
-            for (int t = 1; t <= 2 * R; t++) {
-                const float kt = L.taps.k[t > R ? t - R : R - t];
-                if constexpr (P == kProfileOpenCV)
-                    acc = __builtin_elementwise_fma(v[t], (bd_f2)kt, acc);
-                else
-                    acc = acc + v[t] * kt;
+            for (int t0 = 0; t0 < NT; t0 += BD2_TAPS) {
+#pragma unroll
+                for (int t = t0 + BD2_TAPS; t < t0 + 2 * BD2_TAPS && t < NT; t++) v[t] = p[t];
+#pragma unroll
+                for (int t = t0; t < t0 + BD2_TAPS && t < NT; t++) {
+                    const float kt = L.taps.k[t > R ? t - R : R - t];
+                    if (t == 0)
+                        acc = v[0] * kt;
+                    else if constexpr (P == kProfileOpenCV)
+                        acc = __builtin_elementwise_fma(v[t], (bd_f2)kt, acc);
+                    else
+                        acc = acc + v[t] * kt;
+                }
+                if (t0 + 2 * BD2_TAPS < NT) asm volatile("" : "+v"(acc)::"memory");
             }
             return acc;
         };
@@ -609,6 +636,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_BD2_WP
         };
         auto emit = [&](const ScanMasks& m, int y, int x) {
             uint32_t ok3 = (uint32_t)m.s1 | ((uint32_t)m.s2 << 1) | ((uint32_t)m.s3 << 2);
+            // the key's column field is formed here, on the rare path: hoisted
+            // out of the row loop it holds two registers per half all the way
+            asm volatile("" : "+v"(x));
             while (ok3) {
                 const int bit = __builtin_ctz(ok3);
                 ok3 &= ok3 - 1;
@@ -693,36 +723,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_BD2_WP
             }
             shift();
         };
-        // NB buffer pairs: rows q, q + 1 are processed from one pair while
-        // the next NB - 1 pairs' loads (rows up to q + 2 NB - 1) are in flight
-        RowBuf buf[NB][2];
-        constexpr int GROUP = 2 * NB;
+        // Three row buffers in rotation: a buffer is reloaded (row q + 3) as
+        // soon as its step (row q) is done, so each row's loads are in flight
+        // for two steps.  (Two buffer pairs, rows q + 2 and q + 3 loaded
+        // before steps q and q + 1, held a fourth buffer: 12 registers.)
+        RowBuf buf[3];
+        constexpr int GROUP = 3;
         auto group = [&](int q, auto full_tag) {
 #pragma unroll
-            for (int k = 0; k < NB; k++) {
-                load(q + 2 * k + 2 * (NB - 1), buf[(k + NB - 1) % NB][0], 0);
-                load(q + 2 * k + 2 * (NB - 1) + 1, buf[(k + NB - 1) % NB][1], 1);
+            for (int k = 0; k < GROUP; k++) {
+                step(q + k, buf[k], full_tag);
                 __builtin_amdgcn_sched_barrier(0);
-                step(q + 2 * k, buf[k][0], full_tag);
-                step(q + 2 * k + 1, buf[k][1], full_tag);
+                load(q + k + GROUP, buf[k], k & 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
 #pragma unroll
-        for (int k = 0; k < NB - 1; k++) {
-            load(q0 + 2 * k, buf[k][0], 0);
-            load(q0 + 2 * k + 1, buf[k][1], 1);
-        }
+        for (int k = 0; k < GROUP; k++) load(q0 + k, buf[k], k & 1);
         int q = q0;
         for (; q < ya + R + 1; q += GROUP) group(q, std::false_type{});
-        if constexpr (NB == 2 && U == 3) {
-            // three groups per iteration: the rolling DoG rows (a 3-cycle)
-            // and the buffer pairs (a 2-cycle) return to their registers
-            for (; q + 3 * GROUP - 1 <= q1; q += 3 * GROUP) {
-                group(q, std::true_type{});
-                group(q + GROUP, std::true_type{});
-                group(q + 2 * GROUP, std::true_type{});
-            }
+        // a group returns the rolling DoG rows (a 3-cycle) and the buffers to
+        // their registers; four per iteration spread the window's moves
+        for (; q + 4 * GROUP - 1 <= q1; q += 4 * GROUP) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) group(q + u * GROUP, std::true_type{});
         }
         for (; q + GROUP - 1 <= q1; q += GROUP) group(q, std::true_type{});
         for (; q <= q1; q += GROUP) group(q, std::false_type{});
@@ -788,16 +812,11 @@ int launch_blur_detect(int R, BlurDetectLaunch& L, hipStream_t st, const PathOpt
     L.nsy = (L.H + seg - 1) / seg;
     const long waves = (long)L.nsx * L.nsy * L.n_img;
     const dim3 grid((uint32_t)((waves + 3) / 4));
-    if (pair && o.bd_pair == 2) {
+    if (pair) {
         if (L.profile == kProfileOpenCV)
-            hipLaunchKernelGGL((k_blur_detect_pair<13, kProfileOpenCV, 2, 1>), grid, dim3(256), 0, st, L);
+            hipLaunchKernelGGL((k_blur_detect_pair<13, kProfileOpenCV>), grid, dim3(256), 0, st, L);
         else
-            hipLaunchKernelGGL((k_blur_detect_pair<7, kProfileImageproc, 2, 1>), grid, dim3(256), 0, st, L);
-    } else if (pair) {
-        if (L.profile == kProfileOpenCV)
-            hipLaunchKernelGGL((k_blur_detect_pair<13, kProfileOpenCV, 2, 3>), grid, dim3(256), 0, st, L);
-        else
-            hipLaunchKernelGGL((k_blur_detect_pair<7, kProfileImageproc, 2, 3>), grid, dim3(256), 0, st, L);
+            hipLaunchKernelGGL((k_blur_detect_pair<7, kProfileImageproc>), grid, dim3(256), 0, st, L);
     } else if (L.profile == kProfileOpenCV)
         hipLaunchKernelGGL((k_blur_detect<13, kProfileOpenCV>), grid, dim3(256), 0, st, L);
     else

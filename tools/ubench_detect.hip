@@ -451,7 +451,7 @@ int main(int argc, char** argv) {
     });
     // the pair kernel (two column strips per lane): time, then G_5 and candidates
     const int bdw = getenv("BD_WAVES") ? atoi(getenv("BD_WAVES")) : 8192;
-    for (int mode = 1; mode <= 2; mode++) {
+    for (int mode = 1; mode <= 1; mode++) {
     PathOpts po2{};
     po2.bd_pair = mode;
     po2.bd_waves = bdw;
