@@ -292,6 +292,62 @@ int sift_mi_match_pairs_device(sift_mi_ctx* ctx, const uint8_t* d_desc, const si
                                const sift_mi_seg_pair* pairs, uint32_t n_pairs, float ratio, int cross_check,
                                sift_mi_match* out, size_t cap, size_t* pair_offsets);
 
+/* LABELLED EXTENSION (the crate has nothing like it; examples/sift-match.rs
+ * stops at drawing the matches): geometric verification of matched pairs.
+ * Per pair a RANSAC homography from `iterations` four-match samples, scored
+ * by the count of matches within `threshold` px (in the train image) of the
+ * projected query keypoint, then up to `refit_rounds` least-squares refits on
+ * the inliers.  The rules -- the integer sampling (a function of seed,
+ * hypothesis index and match count only: a pair's place in the call does not
+ * matter), the orientation test of a sample, the f64 minimal solve, the f32
+ * division-free score, ties to the lowest hypothesis, the refit's acceptance
+ * -- are stated in tests/verify_ref.py, and without refits the result equals
+ * that restatement bit for bit. */
+typedef struct {
+    float    threshold;     /* px in the train image, finite, > 0 */
+    uint32_t iterations;    /* hypotheses per pair, 1..65536 */
+    uint32_t seed;
+    uint32_t refit_rounds;  /* 0..8 least-squares refits on the inliers */
+} sift_mi_ransac_params;
+
+typedef struct {
+    float    h[9];            /* row-major, h[8] == 1: (x,y,1) of the query keypoint -> train; all 0 if no model */
+    uint32_t n_matches;       /* the pair's match count */
+    uint32_t n_inliers;       /* 0 if no model */
+    int32_t  best_hypothesis; /* index of the winning sample, -1 if none was valid */
+    uint32_t refits;          /* accepted refit rounds */
+} sift_mi_homography;
+
+/* d_kps, offsets, n_segs, pairs: as sift_mi_device_results and
+ * sift_mi_match_pairs_device use them (keypoints of segment s at
+ * d_kps[offsets[s] .. offsets[s+1])).  matches / pair_offsets: the host
+ * arrays the match call wrote (pair p's matches at matches[pair_offsets[p] ..
+ * pair_offsets[p+1]), segment-relative indices); the caller may have
+ * filtered them.  The call uploads the matches, runs one launch sequence on
+ * the context stream and returns once models[n_pairs] and
+ * inliers[pair_offsets[n_pairs]] (1 = inlier, parallel to matches) are
+ * written; no allocation once the context's scratch has grown to the call's
+ * size.  It only reads d_kps and never invalidates the device results.
+ * A pair with fewer than 4 matches or without a valid sample gets no model
+ * (h all 0, n_inliers 0, best_hypothesis -1, a zero mask): a result, not an
+ * error.  SIFT_MI_EINVAL, checked on the host before any device work (no
+ * kernel sees an index outside its segment): a null argument, a threshold
+ * that is not finite or <= 0, iterations of 0 or above 65536, refit_rounds
+ * above 8, a pair index >= n_segs, decreasing offsets or pair_offsets, a
+ * match index outside its pair's segment. */
+int sift_mi_verify_pairs_device(sift_mi_ctx* ctx, const sift_mi_keypoint* d_kps, const size_t* offsets, uint32_t n_segs,
+                                const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                const sift_mi_match* matches, const size_t* pair_offsets,
+                                const sift_mi_ransac_params* params,
+                                sift_mi_homography* models /* [n_pairs] */, uint8_t* inliers /* [pair_offsets[n_pairs]] */);
+
+/* The one-pair form on host keypoints: uploads them and runs the same
+ * kernels (matches / inliers may be null when n_matches is 0). */
+int sift_mi_verify_matches(sift_mi_ctx* ctx, const sift_mi_keypoint* query_kps, size_t n_query,
+                           const sift_mi_keypoint* train_kps, size_t n_train,
+                           const sift_mi_match* matches, size_t n_matches,
+                           const sift_mi_ransac_params* params, sift_mi_homography* model, uint8_t* inliers);
+
 /* ---- the input step before the path ---------------
  * Baseline (SOF0/SOF1) Huffman JPEG, 1 or 3 components -> 8-bit luma, with
  * the arithmetic of the reference's decode: image 0.25.2 `image::open` /
@@ -369,6 +425,9 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        sift_mi_match_pairs_device (2-NN, ratio test, segment pairs of a
  *        device arena); sift_mi_stats gained match_ms, match_tiles (a larger
  *        struct); sift_mi_device_results stay valid across match calls.
+ *        Added later under the same version (no existing symbol or struct
+ *        changed): sift_mi_verify_pairs_device, sift_mi_verify_matches
+ *        (RANSAC homography + inlier refit of matched pairs).
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

@@ -11,6 +11,6 @@ from .sift import (  # noqa: F401
     match_frames, match_neighbors, match_pairs_device,
     precompute_images, sift,
     sift_with_precomputed,
-    sift_with_processing, stable_sort_xy_size)
+    sift_with_processing, stable_sort_xy_size, verify_frames, verify_matches, verify_pairs_device)
 
 __version__ = "0.1.0"

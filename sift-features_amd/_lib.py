@@ -23,6 +23,7 @@ EXPORTS = [
     "sift_mi_sift_with_precomputed", "sift_mi_compute_descriptor", "sift_mi_gaussian_blur",
     "sift_mi_resize_linear", "sift_mi_resize_nearest", "sift_mi_match_descriptors", "sift_mi_jpeg_dims",
     "sift_mi_match_neighbors", "sift_mi_match_ratio", "sift_mi_match_pairs_device",
+    "sift_mi_verify_pairs_device", "sift_mi_verify_matches",
     "sift_mi_decode_jpeg", "sift_mi_decode_jpeg_batch", "sift_mi_get_stats",
     "sift_mi_reset_stats",
     "sift_mi_version", "sift_mi_last_error",
@@ -50,6 +51,18 @@ class Neighbors(ctypes.Structure):
 class SegPair(ctypes.Structure):
     """include/sift_mi.h sift_mi_seg_pair."""
     _fields_ = [("query_seg", ctypes.c_uint32), ("train_seg", ctypes.c_uint32)]
+
+
+class RansacParams(ctypes.Structure):
+    """include/sift_mi.h sift_mi_ransac_params."""
+    _fields_ = [("threshold", ctypes.c_float), ("iterations", ctypes.c_uint32), ("seed", ctypes.c_uint32),
+                ("refit_rounds", ctypes.c_uint32)]
+
+
+class Homography(ctypes.Structure):
+    """include/sift_mi.h sift_mi_homography (h all 0, best_hypothesis -1: no model)."""
+    _fields_ = [("h", ctypes.c_float * 9), ("n_matches", ctypes.c_uint32), ("n_inliers", ctypes.c_uint32),
+                ("best_hypothesis", ctypes.c_int32), ("refits", ctypes.c_uint32)]
 
 
 class Stats(ctypes.Structure):
@@ -122,6 +135,8 @@ def lib():
         "sift_mi_match_neighbors": [vp, vp, sz, vp, sz, vp],
         "sift_mi_match_ratio": [vp, vp, sz, vp, sz, f32, i32, vp, sz, P(sz)],
         "sift_mi_match_pairs_device": [vp, vp, P(sz), u32, vp, u32, f32, i32, vp, sz, P(sz)],
+        "sift_mi_verify_pairs_device": [vp, vp, P(sz), u32, vp, u32, vp, P(sz), P(RansacParams), vp, vp],
+        "sift_mi_verify_matches": [vp, vp, sz, vp, sz, vp, sz, P(RansacParams), vp, vp],
         "sift_mi_jpeg_dims": [vp, sz, P(u32), P(u32)],
         "sift_mi_decode_jpeg": [vp, vp, sz, vp, sz, i32],
         "sift_mi_decode_jpeg_batch": [vp, P(vp), P(sz), u32, vp, sz, sz, i32],

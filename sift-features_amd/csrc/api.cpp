@@ -317,6 +317,87 @@ int match_upload(sift_mi_ctx* c, const uint8_t* query, size_t nq, const uint8_t*
     if (nt) HIPCHK(hipMemcpyAsync(M.desc.p + nq * kDescSize, train, nt * kDescSize, hipMemcpyHostToDevice, c->stream));
     return 0;
 }
+
+static_assert(sizeof(VerifyMatch) == sizeof(sift_mi_match) && sizeof(VerifyModel) == sizeof(sift_mi_homography) &&
+                  sizeof(OutKp) == sizeof(sift_mi_keypoint),
+              "verify.hip's records are the C ABI's");
+
+int check_ransac(const sift_mi_ransac_params* p) {
+    if (!(std::isfinite(p->threshold) && p->threshold > 0.0f))
+        return fail(SIFT_MI_EINVAL, "threshold must be finite and > 0");
+    if (p->iterations < 1 || p->iterations > 65536) return fail(SIFT_MI_EINVAL, "iterations must be 1..65536");
+    if (p->refit_rounds > 8) return fail(SIFT_MI_EINVAL, "refit_rounds must be 0..8");
+    return 0;
+}
+
+// Verification of the pairs' matches on device keypoints d_kps: checks every
+// segment, pair and match index on the host (no kernel sees an index outside
+// its segment), uploads the matches (and, with d_kps null, the host keypoints
+// h_query / h_train of the two segments), runs the launch sequence on the context
+// stream and returns once models / inliers are written.
+int verify_run(sift_mi_ctx* c, const OutKp* d_kps, const size_t* offsets, uint32_t n_segs,
+               const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
+               const size_t* pair_offsets, const sift_mi_ransac_params* prm, sift_mi_homography* models,
+               uint8_t* inliers, const OutKp* h_query = nullptr, const OutKp* h_train = nullptr) {
+    constexpr size_t kMax = 0x7fffffff;
+    CHK(check_ransac(prm));
+    if (((uintptr_t)d_kps & 3) != 0) return fail(SIFT_MI_EINVAL, "d_kps must be 4-byte aligned");
+    for (uint32_t s = 0; s < n_segs; s++) {
+        if (offsets[s + 1] < offsets[s]) return fail(SIFT_MI_EINVAL, "offsets decrease");
+        if (offsets[s + 1] - offsets[s] > kMax) return fail(SIFT_MI_EINVAL, "segment longer than 2^31 - 1 rows");
+    }
+    const size_t row_base = offsets[0];
+    if (offsets[n_segs] - row_base > kMax) return fail(SIFT_MI_EINVAL, "segments sum to more than 2^31 - 1 rows");
+    for (uint32_t p = 0; p < n_pairs; p++)
+        if (pair_offsets[p + 1] < pair_offsets[p]) return fail(SIFT_MI_EINVAL, "pair_offsets decrease");
+    const size_t m_base = pair_offsets[0], total = pair_offsets[n_pairs] - m_base;
+    if (total > kMax) return fail(SIFT_MI_EINVAL, "more than 2^31 - 1 matches");
+    if (total && (!matches || !inliers)) return fail(SIFT_MI_EINVAL, "null argument");
+    const uint32_t bpp = (prm->iterations + 255) / 256;
+    if ((size_t)n_pairs * bpp > kMax) return fail(SIFT_MI_EINVAL, "pairs x iterations too large");
+    if (n_pairs == 0) return 0;
+    std::vector<VerifyPair> P(n_pairs);
+    for (uint32_t p = 0; p < n_pairs; p++) {
+        const uint32_t qs = pairs[p].query_seg, ts = pairs[p].train_seg;
+        if (qs >= n_segs || ts >= n_segs) return fail(SIFT_MI_EINVAL, "pair names a segment >= n_segs");
+        const size_t nq = offsets[qs + 1] - offsets[qs], nt = offsets[ts + 1] - offsets[ts];
+        for (size_t i = pair_offsets[p]; i < pair_offsets[p + 1]; i++) {
+            const sift_mi_match& mt = matches[i];
+            if (mt.query_idx < 0 || (size_t)mt.query_idx >= nq || mt.train_idx < 0 || (size_t)mt.train_idx >= nt)
+                return fail(SIFT_MI_EINVAL, "match index outside its pair's segment (pair " + std::to_string(p) + ")");
+        }
+        P[p] = VerifyPair{(uint32_t)(pair_offsets[p] - m_base), (uint32_t)(pair_offsets[p + 1] - pair_offsets[p]),
+                          (uint32_t)(offsets[qs] - row_base), (uint32_t)(offsets[ts] - row_base)};
+    }
+
+    CHK(set_device(c));
+    VerifyScratch& V = c->verify;
+    CHK(pool(V.pairs, n_pairs));
+    CHK(pool(V.matches, total));
+    CHK(pool(V.rec, total));
+    CHK(pool(V.models, (size_t)n_pairs * prm->iterations * 9));
+    CHK(pool(V.best, n_pairs));
+    CHK(pool(V.out, n_pairs));
+    CHK(pool(V.mask, total));
+    hipStream_t st = c->stream;
+    if (!d_kps) {  // host keypoints (two segments) as the context's own arena
+        const size_t nq = offsets[1], nt = offsets[2] - offsets[1];
+        CHK(pool(V.kps, nq + nt));
+        if (nq) HIPCHK(hipMemcpyAsync(V.kps.p, h_query, nq * sizeof(OutKp), hipMemcpyHostToDevice, st));
+        if (nt) HIPCHK(hipMemcpyAsync(V.kps.p + nq, h_train, nt * sizeof(OutKp), hipMemcpyHostToDevice, st));
+        d_kps = V.kps.p;
+    }
+    HIPCHK(hipMemcpyAsync(V.pairs.p, P.data(), (size_t)n_pairs * sizeof(VerifyPair), hipMemcpyHostToDevice, st));
+    if (total)
+        HIPCHK(hipMemcpyAsync(V.matches.p, matches + m_base, total * sizeof(VerifyMatch), hipMemcpyHostToDevice, st));
+    launch_verify(d_kps + row_base, V.matches.p, V.pairs.p, (int)n_pairs, (uint32_t)total, prm->threshold,
+                  prm->iterations, prm->seed, prm->refit_rounds, V.rec.p, V.models.p, V.best.p, V.out.p, V.mask.p, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(models, V.out.p, (size_t)n_pairs * sizeof(VerifyModel), hipMemcpyDeviceToHost, st));
+    if (total) HIPCHK(hipMemcpyAsync(inliers + m_base, V.mask.p, total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -778,6 +859,34 @@ int sift_mi_match_neighbors(sift_mi_ctx* c, const uint8_t* query, size_t nq, con
         for (size_t i = 0; i < nq; i++)
             out[i] = sift_mi_neighbors{{idx[2 * i], idx[2 * i + 1]}, {dist[2 * i], dist[2 * i + 1]}};
         return 0;
+    });
+}
+
+// ---- geometric verification (labelled extension; verify.hip) -----------------
+int sift_mi_verify_pairs_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets, uint32_t n_segs,
+                                const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
+                                const size_t* pair_offsets, const sift_mi_ransac_params* params,
+                                sift_mi_homography* models, uint8_t* inliers) {
+    if (!c || !d_kps || !offsets || !pairs || !matches || !pair_offsets || !params || !models || !inliers)
+        return fail(SIFT_MI_EINVAL, "null argument");
+    return match_guard([&]() -> int {
+        return verify_run(c, reinterpret_cast<const OutKp*>(d_kps), offsets, n_segs, pairs, n_pairs, matches,
+                          pair_offsets, params, models, inliers);
+    });
+}
+
+int sift_mi_verify_matches(sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
+                           const sift_mi_keypoint* train_kps, size_t nt, const sift_mi_match* matches, size_t n_matches,
+                           const sift_mi_ransac_params* params, sift_mi_homography* model, uint8_t* inliers) {
+    if (!c || !params || !model || (nq && !query_kps) || (nt && !train_kps) || (n_matches && (!matches || !inliers)))
+        return fail(SIFT_MI_EINVAL, "null argument");
+    if (nq > 0x7fffffff || nt > 0x7fffffff || nq + nt > 0x7fffffff)
+        return fail(SIFT_MI_EINVAL, "keypoint set too large");
+    return match_guard([&]() -> int {
+        const size_t offsets[3] = {0, nq, nq + nt}, po[2] = {0, n_matches};
+        const sift_mi_seg_pair pair{0, 1};
+        return verify_run(c, nullptr, offsets, 2, &pair, 1, matches, po, params, model, inliers,
+                          reinterpret_cast<const OutKp*>(query_kps), reinterpret_cast<const OutKp*>(train_kps));
     });
 }
 

@@ -287,6 +287,19 @@ struct MatchScratch {
     }
 };
 
+// Pooled scratch of the geometric verification (sift_mi_verify_pairs_device,
+// sift_mi_verify_matches): grows on demand, freed with the context.
+struct VerifyScratch {
+    DevBuf<OutKp> kps;  // sift_mi_verify_matches: [query keypoints | train keypoints]
+    DevBuf<VerifyMatch> matches;
+    DevBuf<VerifyPair> pairs;
+    DevBuf<float4> rec;      // per match (x, y, X, Y)
+    DevBuf<float> models;    // per (pair, hypothesis) 9 f32
+    DevBuf<unsigned long long> best;  // per pair (count << 32 | ~hypothesis)
+    DevBuf<VerifyModel> out;
+    DevBuf<uint8_t> mask;
+};
+
 }  // namespace siftmi
 
 struct sift_mi_ctx {
@@ -358,6 +371,7 @@ struct sift_mi_ctx {
     hipGraphExec_t gexec = nullptr;
     uint32_t batch_frames = 0;
     siftmi::MatchScratch match;
+    siftmi::VerifyScratch verify;
     sift_mi_stats stats{};
 };
 

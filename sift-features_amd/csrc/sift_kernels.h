@@ -318,6 +318,32 @@ void launch_match_pairs(const uint8_t* d, const MatchPair* pairs, int n_pairs, u
                         unsigned long long* col_best, int* train_idx, float* dist, int* nb_idx, float* nb_dist,
                         hipStream_t st);
 
+// verify.hip
+// RANSAC homography + inlier refit of matched pairs (LABELLED EXTENSION;
+// tests/verify_ref.py is the definition).  pairs[n_pairs]: the pair's first
+// record / match and its match count, and the first keypoint rows of its two
+// segments.  VerifyMatch / VerifyModel are sift_mi_match / sift_mi_homography.
+struct VerifyPair {
+    uint32_t rec0, m, qrow0, trow0;
+};
+struct VerifyMatch {
+    int32_t query_idx, train_idx;
+    float distance;
+};
+struct VerifyModel {
+    float h[9];
+    uint32_t n_matches, n_inliers;
+    int32_t best_hypothesis;
+    uint32_t refits;
+};
+constexpr int kVerifyChunk = 1024;  // records of a pair in LDS at a time (k_verify_score)
+// matches[n_rec] hold indices the host has checked against their segments.
+// rec[n_rec], models[n_pairs * iterations * 9], best[n_pairs] are scratch;
+// out[n_pairs] and inliers[n_rec] the results.
+void launch_verify(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs, uint32_t n_rec,
+                   float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds, float4* rec, float* models,
+                   unsigned long long* best, VerifyModel* out, uint8_t* inliers, hipStream_t st);
+
 // describe.hip
 // Descriptor work queues: keypoint i belongs to queue i % kDescQueues, which
 // hands out its keypoints in order; 8 counters on separate 128-B lines (one

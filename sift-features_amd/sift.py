@@ -389,6 +389,84 @@ class Context:
             raise ValueError("offsets reach beyond the device results")
         return self.match_pairs_device(d_desc, offsets, pairs, ratio, cross_check)
 
+    # -- geometric verification (LABELLED EXTENSION: not in the crate) --------
+    @staticmethod
+    def _ransac(threshold, iterations, seed, refit_rounds):
+        return _lib.RansacParams(float(threshold), int(iterations), int(seed) & 0xFFFFFFFF, int(refit_rounds))
+
+    @staticmethod
+    def _match_records(matches):
+        """(query_idx, train_idx, distance) triples -> one sift_mi_match array and the triples' offsets."""
+        po = np.zeros(len(matches) + 1, np.int64)
+        po[1:] = np.cumsum([len(m[0]) for m in matches])
+        rec = np.zeros(max(int(po[-1]), 1), np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4")]))
+        for p, m in enumerate(matches):
+            r = rec[po[p]:po[p + 1]]
+            r["query_idx"], r["train_idx"] = m[0], m[1]
+            if len(m) > 2:
+                r["distance"] = m[2]
+        return rec, po
+
+    @staticmethod
+    def _verify_result(model, mask):
+        info = {"n_matches": model.n_matches, "n_inliers": model.n_inliers,
+                "best_hypothesis": model.best_hypothesis, "refits": model.refits}
+        return np.array(model.h[:], np.float32).reshape(3, 3), mask.astype(bool), info
+
+    def verify_pairs_device(self, d_kps_ptr, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0,
+                            refit_rounds=2):
+        """LABELLED EXTENSION (the crate has nothing like it): per pair a RANSAC
+        homography on its matches with up to `refit_rounds` least-squares
+        refits on the inliers (sift_mi_verify_pairs_device; the rules are
+        tests/verify_ref.py's).  d_kps_ptr: device pointer of the keypoints
+        (device_results()[0]); offsets / pairs as for match_pairs_device;
+        matches: the (query_idx, train_idx, distance) triples it returned, one
+        per pair (possibly filtered).  Returns per pair (H (3, 3) f32 mapping
+        the query keypoint's (x, y, 1) to the train image, inlier mask bool,
+        info dict: n_matches, n_inliers, best_hypothesis, refits); H is all
+        zero and best_hypothesis -1 where the pair has no model."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
+            raise ValueError("offsets: n_segs + 1 non-negative row numbers")
+        pr = [(int(a), int(b)) for a, b in pairs]
+        if len(matches) != len(pr):
+            raise ValueError("one (query_idx, train_idx, distance) triple per pair")
+        rec, po = self._match_records(matches)
+        c_offs = (ctypes.c_size_t * len(offs))(*[int(v) for v in offs])
+        c_po = (ctypes.c_size_t * len(po))(*[int(v) for v in po])
+        c_pairs = (_lib.SegPair * max(len(pr), 1))(*[_lib.SegPair(a, b) for a, b in pr])
+        models = (_lib.Homography * max(len(pr), 1))()
+        mask = np.zeros(max(int(po[-1]), 1), np.uint8)
+        prm = self._ransac(threshold, iterations, seed, refit_rounds)
+        check(lib().sift_mi_verify_pairs_device(self._h, ctypes.c_void_p(d_kps_ptr), c_offs, len(offs) - 1, c_pairs,
+                                                len(pr), rec.ctypes.data, c_po, ctypes.byref(prm), models,
+                                                mask.ctypes.data))
+        return [self._verify_result(models[p], mask[po[p]:po[p + 1]]) for p in range(len(pr))]
+
+    def verify_frames(self, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+        """verify_pairs_device on the keypoints the last
+        sift_batch_device(..., fetch=False) left in HBM, e.g. on what
+        match_frames(offsets, pairs, ...) returned."""
+        d_kps, _, n = self.device_results()
+        if int(offsets[-1]) > n:
+            raise ValueError("offsets reach beyond the device results")
+        return self.verify_pairs_device(d_kps, offsets, pairs, matches, threshold, iterations, seed, refit_rounds)
+
+    def verify_matches(self, kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+        """The one-pair form on host keypoints (sift_mi_verify_matches): kps_q /
+        kps_t are (n, 5) f32 keypoint arrays (SiftResult.keypoints_array; only
+        x, y are read), matches one (query_idx, train_idx, distance) triple.
+        Returns (H, inlier mask, info) as verify_pairs_device does per pair."""
+        q = np.ascontiguousarray(kps_q, dtype=np.float32).reshape(-1, 5)
+        t = np.ascontiguousarray(kps_t, dtype=np.float32).reshape(-1, 5)
+        rec, po = self._match_records([matches])
+        model = _lib.Homography()
+        mask = np.zeros(max(int(po[-1]), 1), np.uint8)
+        prm = self._ransac(threshold, iterations, seed, refit_rounds)
+        check(lib().sift_mi_verify_matches(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t), rec.ctypes.data,
+                                           int(po[-1]), ctypes.byref(prm), ctypes.byref(model), mask.ctypes.data))
+        return self._verify_result(model, mask[:po[-1]])
+
     # -- the input step (SURVEY.md 8(f) row 2) ------------------------------
     def decode_jpeg(self, data):
         """Baseline JPEG bytes -> (h, w) u8 luma, as the reference makes its
@@ -588,6 +666,23 @@ def match_frames(offsets, pairs, ratio=None, cross_check=True):
     """Context.match_frames on the default context (its last
     sift_batch_device(..., fetch=False) results)."""
     return default_context().match_frames(offsets, pairs, ratio, cross_check)
+
+
+def verify_pairs_device(d_kps_ptr, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+    """LABELLED EXTENSION: Context.verify_pairs_device on the default context."""
+    return default_context().verify_pairs_device(d_kps_ptr, offsets, pairs, matches, threshold, iterations, seed,
+                                                 refit_rounds)
+
+
+def verify_frames(offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+    """LABELLED EXTENSION: Context.verify_frames on the default context (its
+    last sift_batch_device(..., fetch=False) results)."""
+    return default_context().verify_frames(offsets, pairs, matches, threshold, iterations, seed, refit_rounds)
+
+
+def verify_matches(kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+    """LABELLED EXTENSION: Context.verify_matches on the default context."""
+    return default_context().verify_matches(kps_q, kps_t, matches, threshold, iterations, seed, refit_rounds)
 
 
 def stable_sort_xy_size(keypoints_array):

@@ -1,7 +1,8 @@
 """sift-match: the counterpart of the crate's examples/sift-match.rs on the
 MI355X path.
 
-    python sift-features_amd/sift_match.py <a.jpg> <b.jpg> [--ratio R] [--processing opencv|imageproc] [--device N]
+    python sift-features_amd/sift_match.py <a.jpg> <b.jpg> [--ratio R] [--verify [THR]]
+                                           [--processing opencv|imageproc] [--device N]
 
 examples/sift-match.rs:30-35, :87-97 opens two images, runs `sift()` on each and
 matches the second's descriptors (query) against the first's (train) with
@@ -11,7 +12,10 @@ decoder (jpeg.hip), `sift()` runs on the GPU through the C ABI and the
 matcher is the MFMA kernel of match.hip.  Prints both keypoint counts and the
 number of cross-checked matches.  `--ratio R` (0 < R <= 1) adds Lowe's ratio
 test on the two nearest neighbours, a labelled extension (the crate has
-none).  Exits non-zero (with the library's error) when the HIP library or
+none).  `--verify [THR]` (default 3 px), another labelled extension, fits a
+RANSAC homography to the matches (verify.hip, the defaults of
+Context.verify_matches) and prints a fourth line with its inlier count.
+Exits non-zero (with the library's error) when the HIP library or
 the device is missing: there is no CPU fallback.
 """
 import argparse
@@ -27,6 +31,7 @@ def main(argv=None):
     ap.add_argument("path_a")
     ap.add_argument("path_b")
     ap.add_argument("--ratio", type=float, default=None)
+    ap.add_argument("--verify", type=float, nargs="?", const=3.0, default=None, metavar="THR")
     ap.add_argument("--processing", choices=("imageproc", "opencv"), default="imageproc")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -41,11 +46,16 @@ def main(argv=None):
     try:
         res_a, res_b = (ctx.sift_jpeg(d) for d in datas)
         qi, ti, dist = ctx.match_descriptors(res_b.descriptors, res_a.descriptors, cross_check=True, ratio=a.ratio)
+        if a.verify is not None:
+            _, _, info = ctx.verify_matches(res_b.keypoints_array, res_a.keypoints_array, (qi, ti, dist),
+                                            threshold=a.verify)
     finally:
         ctx.close()
     print(f"{len(res_a)} keypoints")
     print(f"{len(res_b)} keypoints")
     print(f"{len(qi)} matches" + (f" (ratio {a.ratio:g})" if a.ratio is not None else ""))
+    if a.verify is not None:
+        print(f"{info['n_inliers']} inliers (homography, threshold {a.verify:g})")
     return 0
 
 
