@@ -348,6 +348,48 @@ int sift_mi_verify_matches(sift_mi_ctx* ctx, const sift_mi_keypoint* query_kps, 
                            const sift_mi_match* matches, size_t n_matches,
                            const sift_mi_ransac_params* params, sift_mi_homography* model, uint8_t* inliers);
 
+/* LABELLED EXTENSION like the homography above: epipolar verification of
+ * matched pairs, the model for a moving camera in a 3-D scene.  Per pair a
+ * RANSAC fundamental matrix F, (X, Y, 1) F (x, y, 1)^T = 0 for a query
+ * keypoint (x, y) and its train keypoint (X, Y): `iterations` eight-match
+ * samples, each solved by the 8-point method (f64, box-normalised
+ * coordinates, Gaussian elimination with complete pivoting), scored by the
+ * count of matches whose Sampson distance is <= `threshold` px, then up to
+ * `refit_rounds` refits on the inliers (the smallest eigenvector of the
+ * inliers' 9 x 9 moment matrix, made rank 2).  sift_mi_ransac_params is the
+ * homography call's, its threshold read as the Sampson distance in px.  The
+ * rules are stated in tests/epipolar_ref.py, and without refits the result
+ * equals that restatement bit for bit.
+ * F is rank 2, up to its f32 rounding, if and only if refits >= 1; with
+ * refits == 0 it is the raw 8-point solution of the winning sample, which is
+ * not.  Limits: a scene that is one plane (or a camera that only rotates)
+ * satisfies a whole family of F, every match of the plane is an inlier of any
+ * of them, and the homography call is the right tool there; an eight-match
+ * sample is all inliers with probability share^8, so 1024 hypotheses suit
+ * inlier shares >= 0.5 and lower shares need more iterations. */
+typedef struct {
+    float    f[9];            /* row-major, largest entry == 1; all 0 if no model */
+    uint32_t n_matches;       /* the pair's match count */
+    uint32_t n_inliers;       /* 0 if no model */
+    int32_t  best_hypothesis; /* index of the winning sample, -1 if none was valid */
+    uint32_t refits;          /* accepted refit rounds; F is rank 2 iff >= 1 */
+} sift_mi_fundamental;
+
+/* The arguments, the checks (SIFT_MI_EINVAL) and the guarantees of
+ * sift_mi_verify_pairs_device / sift_mi_verify_matches.  A pair with fewer
+ * than 8 matches or without a valid sample gets no model (f all 0, n_inliers
+ * 0, best_hypothesis -1, a zero mask): a result, not an error. */
+int sift_mi_verify_pairs_epipolar_device(sift_mi_ctx* ctx, const sift_mi_keypoint* d_kps, const size_t* offsets,
+                                         uint32_t n_segs, const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                         const sift_mi_match* matches, const size_t* pair_offsets,
+                                         const sift_mi_ransac_params* params,
+                                         sift_mi_fundamental* models /* [n_pairs] */,
+                                         uint8_t* inliers /* [pair_offsets[n_pairs]] */);
+int sift_mi_verify_matches_epipolar(sift_mi_ctx* ctx, const sift_mi_keypoint* query_kps, size_t n_query,
+                                    const sift_mi_keypoint* train_kps, size_t n_train,
+                                    const sift_mi_match* matches, size_t n_matches,
+                                    const sift_mi_ransac_params* params, sift_mi_fundamental* model, uint8_t* inliers);
+
 /* ---- the input step before the path ---------------
  * Baseline (SOF0/SOF1) Huffman JPEG, 1 or 3 components -> 8-bit luma, with
  * the arithmetic of the reference's decode: image 0.25.2 `image::open` /
@@ -427,7 +469,9 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        struct); sift_mi_device_results stay valid across match calls.
  *        Added later under the same version (no existing symbol or struct
  *        changed): sift_mi_verify_pairs_device, sift_mi_verify_matches
- *        (RANSAC homography + inlier refit of matched pairs).
+ *        (RANSAC homography + inlier refit of matched pairs);
+ *        sift_mi_verify_pairs_epipolar_device, sift_mi_verify_matches_epipolar
+ *        (RANSAC fundamental matrix + inlier refit; sift_mi_fundamental).
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

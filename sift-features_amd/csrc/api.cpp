@@ -319,8 +319,10 @@ int match_upload(sift_mi_ctx* c, const uint8_t* query, size_t nq, const uint8_t*
 }
 
 static_assert(sizeof(VerifyMatch) == sizeof(sift_mi_match) && sizeof(VerifyModel) == sizeof(sift_mi_homography) &&
-                  sizeof(OutKp) == sizeof(sift_mi_keypoint),
-              "verify.hip's records are the C ABI's");
+                  sizeof(VerifyModel) == sizeof(sift_mi_fundamental) && sizeof(OutKp) == sizeof(sift_mi_keypoint),
+              "verify.hip's and verify_epipolar.hip's records are the C ABI's");
+
+enum class VerifyKind { Homography, Fundamental };
 
 int check_ransac(const sift_mi_ransac_params* p) {
     if (!(std::isfinite(p->threshold) && p->threshold > 0.0f))
@@ -334,10 +336,11 @@ int check_ransac(const sift_mi_ransac_params* p) {
 // segment, pair and match index on the host (no kernel sees an index outside
 // its segment), uploads the matches (and, with d_kps null, the host keypoints
 // h_query / h_train of the two segments), runs the launch sequence on the context
-// stream and returns once models / inliers are written.
-int verify_run(sift_mi_ctx* c, const OutKp* d_kps, const size_t* offsets, uint32_t n_segs,
+// stream and returns once models / inliers are written.  `models` receives
+// n_pairs sift_mi_homography or sift_mi_fundamental records (one layout).
+int verify_run(sift_mi_ctx* c, VerifyKind kind, const OutKp* d_kps, const size_t* offsets, uint32_t n_segs,
                const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
-               const size_t* pair_offsets, const sift_mi_ransac_params* prm, sift_mi_homography* models,
+               const size_t* pair_offsets, const sift_mi_ransac_params* prm, void* models,
                uint8_t* inliers, const OutKp* h_query = nullptr, const OutKp* h_train = nullptr) {
     constexpr size_t kMax = 0x7fffffff;
     CHK(check_ransac(prm));
@@ -354,7 +357,9 @@ int verify_run(sift_mi_ctx* c, const OutKp* d_kps, const size_t* offsets, uint32
     if (total > kMax) return fail(SIFT_MI_EINVAL, "more than 2^31 - 1 matches");
     if (total && (!matches || !inliers)) return fail(SIFT_MI_EINVAL, "null argument");
     const uint32_t bpp = (prm->iterations + 255) / 256;
-    if ((size_t)n_pairs * bpp > kMax) return fail(SIFT_MI_EINVAL, "pairs x iterations too large");
+    // the epipolar models kernel runs 64 hypotheses per workgroup
+    if ((size_t)n_pairs * bpp * (kind == VerifyKind::Fundamental ? 4 : 1) > kMax)
+        return fail(SIFT_MI_EINVAL, "pairs x iterations too large");
     if (n_pairs == 0) return 0;
     std::vector<VerifyPair> P(n_pairs);
     for (uint32_t p = 0; p < n_pairs; p++) {
@@ -377,6 +382,7 @@ int verify_run(sift_mi_ctx* c, const OutKp* d_kps, const size_t* offsets, uint32
     CHK(pool(V.rec, total));
     CHK(pool(V.models, (size_t)n_pairs * prm->iterations * 9));
     CHK(pool(V.best, n_pairs));
+    if (kind == VerifyKind::Fundamental) CHK(pool(V.box, (size_t)n_pairs * 6));
     CHK(pool(V.out, n_pairs));
     CHK(pool(V.mask, total));
     hipStream_t st = c->stream;
@@ -390,8 +396,14 @@ int verify_run(sift_mi_ctx* c, const OutKp* d_kps, const size_t* offsets, uint32
     HIPCHK(hipMemcpyAsync(V.pairs.p, P.data(), (size_t)n_pairs * sizeof(VerifyPair), hipMemcpyHostToDevice, st));
     if (total)
         HIPCHK(hipMemcpyAsync(V.matches.p, matches + m_base, total * sizeof(VerifyMatch), hipMemcpyHostToDevice, st));
-    launch_verify(d_kps + row_base, V.matches.p, V.pairs.p, (int)n_pairs, (uint32_t)total, prm->threshold,
-                  prm->iterations, prm->seed, prm->refit_rounds, V.rec.p, V.models.p, V.best.p, V.out.p, V.mask.p, st);
+    if (kind == VerifyKind::Fundamental)
+        launch_verify_epipolar(d_kps + row_base, V.matches.p, V.pairs.p, (int)n_pairs, (uint32_t)total, prm->threshold,
+                               prm->iterations, prm->seed, prm->refit_rounds, V.rec.p, V.box.p, V.models.p, V.best.p,
+                               V.out.p, V.mask.p, st);
+    else
+        launch_verify(d_kps + row_base, V.matches.p, V.pairs.p, (int)n_pairs, (uint32_t)total, prm->threshold,
+                      prm->iterations, prm->seed, prm->refit_rounds, V.rec.p, V.models.p, V.best.p, V.out.p, V.mask.p,
+                      st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(models, V.out.p, (size_t)n_pairs * sizeof(VerifyModel), hipMemcpyDeviceToHost, st));
     if (total) HIPCHK(hipMemcpyAsync(inliers + m_base, V.mask.p, total, hipMemcpyDeviceToHost, st));
@@ -862,22 +874,23 @@ int sift_mi_match_neighbors(sift_mi_ctx* c, const uint8_t* query, size_t nq, con
     });
 }
 
-// ---- geometric verification (labelled extension; verify.hip) -----------------
-int sift_mi_verify_pairs_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets, uint32_t n_segs,
-                                const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
-                                const size_t* pair_offsets, const sift_mi_ransac_params* params,
-                                sift_mi_homography* models, uint8_t* inliers) {
+// ---- geometric verification (labelled extensions; verify.hip, verify_epipolar.hip)
+namespace {
+int verify_pairs_device(VerifyKind kind, sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets,
+                        uint32_t n_segs, const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
+                        const size_t* pair_offsets, const sift_mi_ransac_params* params, void* models,
+                        uint8_t* inliers) {
     if (!c || !d_kps || !offsets || !pairs || !matches || !pair_offsets || !params || !models || !inliers)
         return fail(SIFT_MI_EINVAL, "null argument");
     return match_guard([&]() -> int {
-        return verify_run(c, reinterpret_cast<const OutKp*>(d_kps), offsets, n_segs, pairs, n_pairs, matches,
+        return verify_run(c, kind, reinterpret_cast<const OutKp*>(d_kps), offsets, n_segs, pairs, n_pairs, matches,
                           pair_offsets, params, models, inliers);
     });
 }
 
-int sift_mi_verify_matches(sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
-                           const sift_mi_keypoint* train_kps, size_t nt, const sift_mi_match* matches, size_t n_matches,
-                           const sift_mi_ransac_params* params, sift_mi_homography* model, uint8_t* inliers) {
+int verify_matches(VerifyKind kind, sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
+                   const sift_mi_keypoint* train_kps, size_t nt, const sift_mi_match* matches, size_t n_matches,
+                   const sift_mi_ransac_params* params, void* model, uint8_t* inliers) {
     if (!c || !params || !model || (nq && !query_kps) || (nt && !train_kps) || (n_matches && (!matches || !inliers)))
         return fail(SIFT_MI_EINVAL, "null argument");
     if (nq > 0x7fffffff || nt > 0x7fffffff || nq + nt > 0x7fffffff)
@@ -885,9 +898,42 @@ int sift_mi_verify_matches(sift_mi_ctx* c, const sift_mi_keypoint* query_kps, si
     return match_guard([&]() -> int {
         const size_t offsets[3] = {0, nq, nq + nt}, po[2] = {0, n_matches};
         const sift_mi_seg_pair pair{0, 1};
-        return verify_run(c, nullptr, offsets, 2, &pair, 1, matches, po, params, model, inliers,
+        return verify_run(c, kind, nullptr, offsets, 2, &pair, 1, matches, po, params, model, inliers,
                           reinterpret_cast<const OutKp*>(query_kps), reinterpret_cast<const OutKp*>(train_kps));
     });
+}
+}  // namespace
+
+int sift_mi_verify_pairs_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets, uint32_t n_segs,
+                                const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
+                                const size_t* pair_offsets, const sift_mi_ransac_params* params,
+                                sift_mi_homography* models, uint8_t* inliers) {
+    return verify_pairs_device(VerifyKind::Homography, c, d_kps, offsets, n_segs, pairs, n_pairs, matches, pair_offsets,
+                               params, models, inliers);
+}
+
+int sift_mi_verify_matches(sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
+                           const sift_mi_keypoint* train_kps, size_t nt, const sift_mi_match* matches, size_t n_matches,
+                           const sift_mi_ransac_params* params, sift_mi_homography* model, uint8_t* inliers) {
+    return verify_matches(VerifyKind::Homography, c, query_kps, nq, train_kps, nt, matches, n_matches, params, model,
+                          inliers);
+}
+
+int sift_mi_verify_pairs_epipolar_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets,
+                                         uint32_t n_segs, const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                         const sift_mi_match* matches, const size_t* pair_offsets,
+                                         const sift_mi_ransac_params* params, sift_mi_fundamental* models,
+                                         uint8_t* inliers) {
+    return verify_pairs_device(VerifyKind::Fundamental, c, d_kps, offsets, n_segs, pairs, n_pairs, matches,
+                               pair_offsets, params, models, inliers);
+}
+
+int sift_mi_verify_matches_epipolar(sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
+                                    const sift_mi_keypoint* train_kps, size_t nt, const sift_mi_match* matches,
+                                    size_t n_matches, const sift_mi_ransac_params* params, sift_mi_fundamental* model,
+                                    uint8_t* inliers) {
+    return verify_matches(VerifyKind::Fundamental, c, query_kps, nq, train_kps, nt, matches, n_matches, params, model,
+                          inliers);
 }
 
 int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height) {

@@ -295,6 +295,7 @@ struct VerifyScratch {
     DevBuf<VerifyPair> pairs;
     DevBuf<float4> rec;      // per match (x, y, X, Y)
     DevBuf<float> models;    // per (pair, hypothesis) 9 f32
+    DevBuf<double> box;      // epipolar model: per pair the six f64 values of its box normalisation
     DevBuf<unsigned long long> best;  // per pair (count << 32 | ~hypothesis)
     DevBuf<VerifyModel> out;
     DevBuf<uint8_t> mask;

@@ -344,6 +344,19 @@ void launch_verify(const OutKp* kps, const VerifyMatch* matches, const VerifyPai
                    float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds, float4* rec, float* models,
                    unsigned long long* best, VerifyModel* out, uint8_t* inliers, hipStream_t st);
 
+void launch_verify_gather(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs,
+                          uint32_t n_rec, float4* rec, hipStream_t st);
+
+// verify_epipolar.hip
+// RANSAC fundamental matrix + eigen-refit of matched pairs (LABELLED
+// EXTENSION; tests/epipolar_ref.py is the definition).  The arguments are
+// launch_verify's, plus box[n_pairs * 6] (scratch: the f64 box normalisation
+// of each pair); VerifyModel is sift_mi_fundamental as well (h holds F).
+void launch_verify_epipolar(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs,
+                            uint32_t n_rec, float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds,
+                            float4* rec, double* box, float* models, unsigned long long* best, VerifyModel* out,
+                            uint8_t* inliers, hipStream_t st);
+
 // describe.hip
 // Descriptor work queues: keypoint i belongs to queue i % kDescQueues, which
 // hands out its keypoints in order; 8 counters on separate 128-B lines (one

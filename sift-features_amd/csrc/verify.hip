@@ -18,43 +18,14 @@
 //                     the pair's slot with one 64-bit atomicMax
 //   k_verify_finish   one workgroup per pair: the winner's mask, the refit
 //                     rounds, the sift_mi_homography record
-#include "sift_common.h"
-#include "sift_kernels.h"
+#include "verify_common.h"
 
 namespace siftmi {
 
 namespace {
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// Four distinct indices below m >= 4: draw k is uniform over the m - k indices
-// not yet picked (stepped over in ascending order), so there is no rejection.
-__device__ __forceinline__ void sample4(uint32_t seed, uint32_t h, uint32_t m, uint32_t (&pick)[4]) {
-    const uint32_t s = mix32(mix32(seed + 0x9E3779B9u) ^ h);
-    uint32_t sorted[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t u = mix32(s + 0x85EBCA6Bu * (uint32_t)(k + 1));
-        uint32_t idx = (uint32_t)(((uint64_t)u * (uint64_t)(m - (uint32_t)k)) >> 32);
-#pragma unroll
-        for (int j = 0; j < k; j++) idx += idx >= sorted[j] ? 1u : 0u;
-        pick[k] = idx;
-        sorted[k] = idx;
-#pragma unroll
-        for (int j = k; j > 0; j--) {
-            const uint32_t a = sorted[j - 1], b = sorted[j];
-            sorted[j - 1] = min(a, b);
-            sorted[j] = max(a, b);
-        }
-    }
-}
+using vfy::finite9;
+using vfy::wave_sum;
 
 __device__ __forceinline__ double area2(double ax, double ay, double bx, double by, double cx, double cy) {
     return (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
@@ -93,23 +64,13 @@ __device__ __forceinline__ bool inlier(const float (&h)[9], const float4 r, floa
     return w > 0.0f && du * du + dv * dv <= t2 * (w * w);
 }
 
-__device__ __forceinline__ bool finite9(const float (&h)[9]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 9; k++) ok = ok && isfinite(h[k]);
-    return ok;
-}
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, m), hi = __shfl_xor((uint32_t)(v >> 32), m);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
+struct HomographyModel {
+    static constexpr uint32_t kMinMatches = 4;
+    static __device__ __forceinline__ bool valid(const float (&h)[9]) { return h[8] == 1.0f; }
+    static __device__ __forceinline__ bool inlier(const float (&h)[9], const float4 r, float t2) {
+        return siftmi::inlier(h, r, t2);
+    }
+};
 
 }  // namespace
 
@@ -142,7 +103,7 @@ __global__ __launch_bounds__(256) void k_verify_models(const float4* __restrict_
     const VerifyPair P = pairs[p];
     if (h >= iterations || P.m < 4) return;
     uint32_t pick[4];
-    sample4(seed, h, P.m, pick);
+    vfy::sample_distinct<4>(seed, h, P.m, pick);
     double x[4], y[4], X[4], Y[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -185,39 +146,7 @@ __global__ __launch_bounds__(256) void k_verify_score(const float4* __restrict__
                                                       unsigned long long* __restrict__ best) {
     __shared__ float4 s_rec[kVerifyChunk];
     __shared__ unsigned long long s_key[4];
-    const uint32_t p = blockIdx.x / blocks_per_pair;
-    const uint32_t h = (blockIdx.x % blocks_per_pair) * 256u + threadIdx.x;
-    const VerifyPair P = pairs[p];
-    if (P.m < 4) return;  // the whole workgroup
-    float g[9];
-    const bool live = h < iterations;
-    const float* src = models + ((size_t)p * iterations + (live ? h : 0u)) * 9;
-#pragma unroll
-    for (int k = 0; k < 9; k++) g[k] = src[k];
-    const bool valid = live && g[8] == 1.0f;  // an invalid sample is stored as zeros
-    const float t2 = thr * thr;
-    uint32_t cnt = 0;
-    for (uint32_t c0 = 0; c0 < P.m; c0 += kVerifyChunk) {
-        const uint32_t n = min((uint32_t)kVerifyChunk, P.m - c0);
-        __syncthreads();
-        for (uint32_t j = threadIdx.x; j < n; j += 256u) s_rec[j] = rec[(size_t)P.rec0 + c0 + j];
-        __syncthreads();
-#pragma unroll 4
-        for (uint32_t j = 0; j < n; j++) cnt += inlier(g, s_rec[j], t2) ? 1u : 0u;
-    }
-    uint64_t key = valid ? ((uint64_t)cnt << 32) | (uint32_t)~h : 0ull;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const uint64_t o = shfl_xor_u64(key, s);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < 4; w++) key = s_key[w] > key ? s_key[w] : key;
-        if (key) atomicMax(&best[p], (unsigned long long)key);
-    }
+    vfy::score_body<HomographyModel>(rec, pairs, models, iterations, blocks_per_pair, thr, best, s_rec, s_key);
 }
 
 constexpr int kVerifySums = 23;
@@ -432,6 +361,12 @@ __global__ __launch_bounds__(256) void k_verify_finish(const float4* __restrict_
     }
 }
 
+void launch_verify_gather(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs,
+                          uint32_t n_rec, float4* rec, hipStream_t st) {
+    hipLaunchKernelGGL(k_verify_gather, dim3((n_rec + 255u) / 256u), dim3(256), 0, st, kps, matches, pairs, n_pairs,
+                       n_rec, rec);
+}
+
 void launch_verify(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs, uint32_t n_rec,
                    float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds, float4* rec, float* models,
                    unsigned long long* best, VerifyModel* out, uint8_t* inliers, hipStream_t st) {
@@ -439,8 +374,7 @@ void launch_verify(const OutKp* kps, const VerifyMatch* matches, const VerifyPai
     const uint32_t bpp = (iterations + 255u) / 256u;
     (void)hipMemsetAsync(best, 0, (size_t)n_pairs * 8, st);
     if (n_rec) {
-        hipLaunchKernelGGL(k_verify_gather, dim3((n_rec + 255u) / 256u), dim3(256), 0, st, kps, matches, pairs, n_pairs,
-                           n_rec, rec);
+        launch_verify_gather(kps, matches, pairs, n_pairs, n_rec, rec, st);
         hipLaunchKernelGGL(k_verify_models, dim3((uint32_t)n_pairs * bpp), dim3(256), 0, st, rec, pairs, seed, iterations,
                            bpp, models);
         hipLaunchKernelGGL(k_verify_score, dim3((uint32_t)n_pairs * bpp), dim3(256), 0, st, rec, pairs, models,

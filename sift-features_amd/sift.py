@@ -411,10 +411,20 @@ class Context:
     def _verify_result(model, mask):
         info = {"n_matches": model.n_matches, "n_inliers": model.n_inliers,
                 "best_hypothesis": model.best_hypothesis, "refits": model.refits}
-        return np.array(model.h[:], np.float32).reshape(3, 3), mask.astype(bool), info
+        values = model.f if isinstance(model, _lib.Fundamental) else model.h
+        return np.array(values[:], np.float32).reshape(3, 3), mask.astype(bool), info
+
+    @staticmethod
+    def _verify_model(model):
+        """The record type and the two entry points of `model`."""
+        if model == "homography":
+            return _lib.Homography, lib().sift_mi_verify_pairs_device, lib().sift_mi_verify_matches
+        if model == "fundamental":
+            return _lib.Fundamental, lib().sift_mi_verify_pairs_epipolar_device, lib().sift_mi_verify_matches_epipolar
+        raise ValueError(f"model must be 'homography' or 'fundamental', not {model!r}")
 
     def verify_pairs_device(self, d_kps_ptr, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0,
-                            refit_rounds=2):
+                            refit_rounds=2, model="homography"):
         """LABELLED EXTENSION (the crate has nothing like it): per pair a RANSAC
         homography on its matches with up to `refit_rounds` least-squares
         refits on the inliers (sift_mi_verify_pairs_device; the rules are
@@ -424,7 +434,19 @@ class Context:
         per pair (possibly filtered).  Returns per pair (H (3, 3) f32 mapping
         the query keypoint's (x, y, 1) to the train image, inlier mask bool,
         info dict: n_matches, n_inliers, best_hypothesis, refits); H is all
-        zero and best_hypothesis -1 where the pair has no model."""
+        zero and best_hypothesis -1 where the pair has no model.
+
+        model="fundamental" (another labelled extension, for a moving camera
+        in a 3-D scene) fits a RANSAC fundamental matrix instead
+        (sift_mi_verify_pairs_epipolar_device; tests/epipolar_ref.py): 8-point
+        samples, `threshold` is the Sampson distance in px, and the first
+        item is F (3, 3) f32 with (X, Y, 1) F (x, y, 1)^T = 0 for a query
+        keypoint (x, y) and its train keypoint (X, Y), largest entry 1.  F is
+        rank 2 (up to f32 rounding) iff info["refits"] >= 1, the raw 8-point
+        solution otherwise; a pair needs 8 matches.  A planar scene satisfies
+        a family of F (use the homography there), and 1024 hypotheses suit
+        inlier shares >= 0.5.  Any other `model` raises ValueError."""
+        record, call, _ = self._verify_model(model)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
             raise ValueError("offsets: n_segs + 1 non-negative row numbers")
@@ -435,37 +457,43 @@ class Context:
         c_offs = (ctypes.c_size_t * len(offs))(*[int(v) for v in offs])
         c_po = (ctypes.c_size_t * len(po))(*[int(v) for v in po])
         c_pairs = (_lib.SegPair * max(len(pr), 1))(*[_lib.SegPair(a, b) for a, b in pr])
-        models = (_lib.Homography * max(len(pr), 1))()
+        models = (record * max(len(pr), 1))()
         mask = np.zeros(max(int(po[-1]), 1), np.uint8)
         prm = self._ransac(threshold, iterations, seed, refit_rounds)
-        check(lib().sift_mi_verify_pairs_device(self._h, ctypes.c_void_p(d_kps_ptr), c_offs, len(offs) - 1, c_pairs,
-                                                len(pr), rec.ctypes.data, c_po, ctypes.byref(prm), models,
-                                                mask.ctypes.data))
+        check(call(self._h, ctypes.c_void_p(d_kps_ptr), c_offs, len(offs) - 1, c_pairs, len(pr), rec.ctypes.data, c_po,
+                   ctypes.byref(prm), models, mask.ctypes.data))
         return [self._verify_result(models[p], mask[po[p]:po[p + 1]]) for p in range(len(pr))]
 
-    def verify_frames(self, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+    def verify_frames(self, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
+                      model="homography"):
         """verify_pairs_device on the keypoints the last
         sift_batch_device(..., fetch=False) left in HBM, e.g. on what
         match_frames(offsets, pairs, ...) returned."""
+        self._verify_model(model)
         d_kps, _, n = self.device_results()
         if int(offsets[-1]) > n:
             raise ValueError("offsets reach beyond the device results")
-        return self.verify_pairs_device(d_kps, offsets, pairs, matches, threshold, iterations, seed, refit_rounds)
+        return self.verify_pairs_device(d_kps, offsets, pairs, matches, threshold, iterations, seed, refit_rounds,
+                                        model=model)
 
-    def verify_matches(self, kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+    def verify_matches(self, kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
+                       model="homography"):
         """The one-pair form on host keypoints (sift_mi_verify_matches): kps_q /
         kps_t are (n, 5) f32 keypoint arrays (SiftResult.keypoints_array; only
         x, y are read), matches one (query_idx, train_idx, distance) triple.
-        Returns (H, inlier mask, info) as verify_pairs_device does per pair."""
+        Returns (H, inlier mask, info) as verify_pairs_device does per pair,
+        (F, inlier mask, info) with model="fundamental"
+        (sift_mi_verify_matches_epipolar)."""
+        record, _, call = self._verify_model(model)
         q = np.ascontiguousarray(kps_q, dtype=np.float32).reshape(-1, 5)
         t = np.ascontiguousarray(kps_t, dtype=np.float32).reshape(-1, 5)
         rec, po = self._match_records([matches])
-        model = _lib.Homography()
+        out = record()
         mask = np.zeros(max(int(po[-1]), 1), np.uint8)
         prm = self._ransac(threshold, iterations, seed, refit_rounds)
-        check(lib().sift_mi_verify_matches(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t), rec.ctypes.data,
-                                           int(po[-1]), ctypes.byref(prm), ctypes.byref(model), mask.ctypes.data))
-        return self._verify_result(model, mask[:po[-1]])
+        check(call(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t), rec.ctypes.data, int(po[-1]),
+                   ctypes.byref(prm), ctypes.byref(out), mask.ctypes.data))
+        return self._verify_result(out, mask[:po[-1]])
 
     # -- the input step (SURVEY.md 8(f) row 2) ------------------------------
     def decode_jpeg(self, data):
@@ -668,21 +696,23 @@ def match_frames(offsets, pairs, ratio=None, cross_check=True):
     return default_context().match_frames(offsets, pairs, ratio, cross_check)
 
 
-def verify_pairs_device(d_kps_ptr, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+def verify_pairs_device(d_kps_ptr, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
+                        model="homography"):
     """LABELLED EXTENSION: Context.verify_pairs_device on the default context."""
     return default_context().verify_pairs_device(d_kps_ptr, offsets, pairs, matches, threshold, iterations, seed,
-                                                 refit_rounds)
+                                                 refit_rounds, model)
 
 
-def verify_frames(offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+def verify_frames(offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
+                  model="homography"):
     """LABELLED EXTENSION: Context.verify_frames on the default context (its
     last sift_batch_device(..., fetch=False) results)."""
-    return default_context().verify_frames(offsets, pairs, matches, threshold, iterations, seed, refit_rounds)
+    return default_context().verify_frames(offsets, pairs, matches, threshold, iterations, seed, refit_rounds, model)
 
 
-def verify_matches(kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2):
+def verify_matches(kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2, model="homography"):
     """LABELLED EXTENSION: Context.verify_matches on the default context."""
-    return default_context().verify_matches(kps_q, kps_t, matches, threshold, iterations, seed, refit_rounds)
+    return default_context().verify_matches(kps_q, kps_t, matches, threshold, iterations, seed, refit_rounds, model)
 
 
 def stable_sort_xy_size(keypoints_array):

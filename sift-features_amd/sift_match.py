@@ -2,6 +2,7 @@
 MI355X path.
 
     python sift-features_amd/sift_match.py <a.jpg> <b.jpg> [--ratio R] [--verify [THR]]
+                                           [--model homography|fundamental]
                                            [--processing opencv|imageproc] [--device N]
 
 examples/sift-match.rs:30-35, :87-97 opens two images, runs `sift()` on each and
@@ -14,7 +15,9 @@ number of cross-checked matches.  `--ratio R` (0 < R <= 1) adds Lowe's ratio
 test on the two nearest neighbours, a labelled extension (the crate has
 none).  `--verify [THR]` (default 3 px), another labelled extension, fits a
 RANSAC homography to the matches (verify.hip, the defaults of
-Context.verify_matches) and prints a fourth line with its inlier count.
+Context.verify_matches) and prints a fourth line with its inlier count;
+with `--model fundamental` (only read with --verify) it fits a RANSAC
+fundamental matrix instead (verify_epipolar.hip; THR is the Sampson distance).
 Exits non-zero (with the library's error) when the HIP library or
 the device is missing: there is no CPU fallback.
 """
@@ -32,6 +35,7 @@ def main(argv=None):
     ap.add_argument("path_b")
     ap.add_argument("--ratio", type=float, default=None)
     ap.add_argument("--verify", type=float, nargs="?", const=3.0, default=None, metavar="THR")
+    ap.add_argument("--model", choices=["homography", "fundamental"], default="homography")
     ap.add_argument("--processing", choices=("imageproc", "opencv"), default="imageproc")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -48,14 +52,14 @@ def main(argv=None):
         qi, ti, dist = ctx.match_descriptors(res_b.descriptors, res_a.descriptors, cross_check=True, ratio=a.ratio)
         if a.verify is not None:
             _, _, info = ctx.verify_matches(res_b.keypoints_array, res_a.keypoints_array, (qi, ti, dist),
-                                            threshold=a.verify)
+                                            threshold=a.verify, model=a.model)
     finally:
         ctx.close()
     print(f"{len(res_a)} keypoints")
     print(f"{len(res_b)} keypoints")
     print(f"{len(qi)} matches" + (f" (ratio {a.ratio:g})" if a.ratio is not None else ""))
     if a.verify is not None:
-        print(f"{info['n_inliers']} inliers (homography, threshold {a.verify:g})")
+        print(f"{info['n_inliers']} inliers ({a.model}, threshold {a.verify:g})")
     return 0
 
 

@@ -16,6 +16,11 @@ Then, in this one process:
       device-to-host copy of the keypoint arena) and run the numpy
       restatement (tests/verify_ref.py) once per pair.
 
+--model fundamental measures the epipolar model instead (verify_epipolar.hip;
+the restatement is tests/epipolar_ref.py) and, in the same run, times
+verify_frames with model="homography" as its yardstick
+("homography_verify_frames_ms").
+
 The synthetic frames are independent, so the matches are wrong ones and the
 models meaningless; the cost does not depend on that except in the refit.
 Reports how many pairs (a) and (b) agree on (mask and counts): every pair
@@ -25,6 +30,7 @@ Each GPU step runs under its own time limit (SIGALRM); run the tool itself
 under `timeout` as well.  Prints one JSON line; exits non-zero unless (a) is
 faster than (b) and the two agree without refits.
     python tools/bench_verify.py [--frames 128] [--steps 5] [--host-steps 1] [--ratio 0.8]
+                                 [--model homography|fundamental]
 """
 import argparse
 import contextlib
@@ -63,12 +69,16 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--host-steps", type=int, default=1)
     ap.add_argument("--ratio", type=float, default=0.8)
+    ap.add_argument("--model", choices=["homography", "fundamental"], default="homography")
     a = ap.parse_args()
     import torch
     import pkg_loader
     import shard
     import synth
-    import verify_ref
+    if a.model == "fundamental":
+        import epipolar_ref as verify_ref
+    else:
+        import verify_ref
     pkg = pkg_loader.load()
     n, W, H = a.frames, a.width, a.height
     pairs = [(i, i + 1) for i in range(n - 1)]
@@ -83,18 +93,28 @@ def main():
 
     # (a)
     with limit(120, "verify_frames warm-up"):
-        got = ctx.verify_frames(offs, pairs, matches)  # grows the scratch
+        got = ctx.verify_frames(offs, pairs, matches, model=a.model)  # grows the scratch
     ts = []
     with limit(120, "verify_frames"):
         for _ in range(a.steps):
             t0 = time.perf_counter()
-            got = ctx.verify_frames(offs, pairs, matches)
+            got = ctx.verify_frames(offs, pairs, matches, model=a.model)
             ts.append(time.perf_counter() - t0)
     a_ms = 1e3 * float(np.median(ts))
     with limit(120, "verify_frames, no refit"):
         t0 = time.perf_counter()
-        plain = ctx.verify_frames(offs, pairs, matches, refit_rounds=0)
+        plain = ctx.verify_frames(offs, pairs, matches, refit_rounds=0, model=a.model)
         plain_ms = 1e3 * (time.perf_counter() - t0)
+    yard = {}
+    if a.model != "homography":  # the yardstick, in the same run
+        th = []
+        with limit(120, "verify_frames, homography"):
+            ctx.verify_frames(offs, pairs, matches)
+            for _ in range(a.steps):
+                t0 = time.perf_counter()
+                ctx.verify_frames(offs, pairs, matches)
+                th.append(time.perf_counter() - t0)
+        yard = {"homography_verify_frames_ms": 1e3 * float(np.median(th)), "homography_all_ms": [1e3 * t for t in th]}
 
     # (b)
     def host_route(rounds):
@@ -109,8 +129,9 @@ def main():
             ref = host_route(2)
             tb.append(time.perf_counter() - t0)
     if not tb:  # --host-steps 0: (a) alone, e.g. under a profiler
-        print(json.dumps({"frames": n, "pairs": len(pairs), "ratio": a.ratio, "matches": n_matches,
-                          "a_verify_frames_ms": a_ms, "a_all_ms": [1e3 * t for t in ts], "a_no_refit_ms": plain_ms}))
+        print(json.dumps({"model": a.model, "frames": n, "pairs": len(pairs), "ratio": a.ratio, "matches": n_matches,
+                          "a_verify_frames_ms": a_ms, "a_all_ms": [1e3 * t for t in ts], "a_no_refit_ms": plain_ms,
+                          **yard}))
         ctx.close()
         return 0
     b_ms = 1e3 * float(np.median(tb))
@@ -123,10 +144,11 @@ def main():
     exact0 = sum(bool(g[2] == r[2] and np.array_equal(g[1], r[1]) and
                       np.array_equal(g[0].view(np.uint32), r[0].view(np.uint32))) for g, r in zip(plain, ref0))
     print(json.dumps({
-        "what": "RANSAC homography + refit of the matched consecutive frames of a device-resident batch",
+        "what": f"RANSAC {a.model} + refit of the matched consecutive frames of a device-resident batch",
+        "model": a.model,
         "frames": n, "frame": f"{W}x{H}", "pairs": len(pairs), "keypoints": int(offs[-1]),
         "ratio": a.ratio, "matches": n_matches, "steps": a.steps,
-        "a_verify_frames_ms": a_ms, "a_all_ms": [1e3 * t for t in ts], "a_no_refit_ms": plain_ms,
+        "a_verify_frames_ms": a_ms, "a_all_ms": [1e3 * t for t in ts], "a_no_refit_ms": plain_ms, **yard,
         "b_fetch_then_numpy_ms": b_ms, "b_all_ms": [1e3 * t for t in tb], "b_over_a": b_ms / a_ms,
         "inliers": sum(g[2]["n_inliers"] for g in got), "models": sum(g[2]["best_hypothesis"] >= 0 for g in got),
         "refits": sum(g[2]["refits"] for g in got),
