@@ -194,12 +194,15 @@ typedef enum {
                                       kernel */
     SIFT_MI_PATH_BD_WAVES = 14,    /* the pair kernel's fewest waves per launch when choosing its row
                                       segments, 1024..65536 */
-    SIFT_MI_PATH_CHUNK_MODE = 15   /* automatic chunking: 1 (default) as few chunks as ~64 GB of pyramid
+    SIFT_MI_PATH_CHUNK_MODE = 15,  /* automatic chunking: 1 (default) as few chunks as ~64 GB of pyramid
                                       (counted at 44 B per octave pixel) and ~1062 M seed pixels per chunk
                                       allow (128 x 1080p: one chunk); 0 at least two chunks per
                                       multi-frame call (both pipeline lanes busy), <= ~32 GB / ~531 M
                                       seed pixels each (rounds 1-5).  Either way a chunk is capped at
                                       40% of the device memory the context could use */
+    SIFT_MI_PATH_GUIDED_CULL = 16  /* guided matcher: 1 (default) a wave whose 64 x 64 block of a tile holds
+                                      no admissible element skips its loads and MFMAs; 0 every wave runs them.
+                                      The same bits either way (a diagnostic, not a tuning knob) */
 } sift_mi_path_option;
 int sift_mi_set_path_option(sift_mi_ctx* ctx, int option, int value);
 
@@ -390,6 +393,72 @@ int sift_mi_verify_matches_epipolar(sift_mi_ctx* ctx, const sift_mi_keypoint* qu
                                     const sift_mi_match* matches, size_t n_matches,
                                     const sift_mi_ransac_params* params, sift_mi_fundamental* model, uint8_t* inliers);
 
+/* LABELLED EXTENSION (the step after the verification): guided matching.  The
+ * pairs are matched again like sift_mi_match_pairs_device, but a query
+ * keypoint competes only for the train keypoints the pair's model admits.
+ * Element (i, j) of a pair is admissible when the verification's own inlier
+ * test -- the same f32 operations in the same order -- holds for the record
+ * (x_i, y_i, X_j, Y_j) under the pair's model and `threshold`:
+ * SIFT_MI_MODEL_HOMOGRAPHY the test of sift_mi_verify_pairs_device (threshold
+ * in px of the train image, and the query must lie in front of the
+ * homography's horizon), SIFT_MI_MODEL_FUNDAMENTAL the Sampson test of
+ * sift_mi_verify_pairs_epipolar_device (threshold = Sampson distance in px).
+ * Nearest / second nearest (lowest (integer L2^2, index)), the distance and
+ * the cross check are the unguided matcher's over the admissible elements
+ * only: with cross_check, query i is kept only if its nearest admissible
+ * train row's nearest admissible query is i.  The rule is stated in
+ * tests/guided_ref.py and the result equals it bit for bit.
+ *   ratio         > 0: kept only if distance[0] < ratio * distance[1] (f32,
+ *                 one multiply, strict).  A query with exactly ONE admissible
+ *                 candidate has no second neighbour, distance[1] = +inf, and
+ *                 PASSES -- unlike sift_mi_match_ratio, which rejects a query
+ *                 without a second neighbour: under a 3 px homography gate
+ *                 most true matches have a single candidate.
+ *   max_distance  > 0: kept only if distance[0] <= max_distance (the guard for
+ *                 a lone candidate with an unrelated descriptor); 0: no cap.
+ * A query with no admissible candidate has no match, and a pair whose model
+ * is nine zeros (what the verification writes for "no model") gets an empty
+ * range: a result, not an error.  With cross_check, ratio 0, no cap and the
+ * verification's own model and threshold, every inlier of a verified
+ * cross-checked match set is in the guided result.
+ * Limits inherited from the verification: a scene that is one plane satisfies
+ * a family of F, so under SIFT_MI_MODEL_FUNDAMENTAL the gate there is only as
+ * good as the F that happened to win (use the homography); and an F gate
+ * admits the whole band around an epipolar line, far more candidates than an
+ * H gate's disc, so ratio and max_distance matter more with it.
+ * models: n_pairs * 9 host f32, row-major, as sift_mi_homography.h /
+ * sift_mi_fundamental.f.  d_desc, d_kps, offsets, pairs, out, cap,
+ * pair_offsets: as sift_mi_match_pairs_device and sift_mi_verify_pairs_device
+ * use them (segment-relative indices, query order, pair after pair; if cap is
+ * too small, SIFT_MI_EINVAL with pair_offsets[n_pairs] set to the needed
+ * count).  SIFT_MI_EINVAL, checked on the host before any device work: a
+ * null argument, an unknown model_kind, a threshold that is not finite or
+ * <= 0, a bad ratio (as sift_mi_match_ratio), a negative or NaN max_distance,
+ * a model entry that is not finite, a pair index >= n_segs, decreasing
+ * offsets.  The call only reads d_desc and d_kps and never invalidates the
+ * device results; no allocation once the context's scratch has grown to the
+ * call's size; its kernel time is added to sift_mi_stats.match_ms. */
+typedef enum { SIFT_MI_MODEL_HOMOGRAPHY = 0, SIFT_MI_MODEL_FUNDAMENTAL = 1 } sift_mi_model_kind;
+typedef struct {
+    float threshold, ratio, max_distance;
+    int cross_check;
+} sift_mi_guided_params;
+int sift_mi_match_pairs_guided_device(sift_mi_ctx* ctx, const uint8_t* d_desc, const sift_mi_keypoint* d_kps,
+                                      const size_t* offsets, uint32_t n_segs, const sift_mi_seg_pair* pairs,
+                                      uint32_t n_pairs, int model_kind, const float* models /* n_pairs * 9 */,
+                                      const sift_mi_guided_params* params, sift_mi_match* out, size_t cap,
+                                      size_t* pair_offsets);
+/* The one-pair form on host descriptors and host keypoints: uploads them and
+ * runs the same kernels; *n_matches as sift_mi_match_ratio sets it. */
+int sift_mi_match_guided(sift_mi_ctx* ctx, const uint8_t* query, const sift_mi_keypoint* query_kps, size_t n_query,
+                         const uint8_t* train, const sift_mi_keypoint* train_kps, size_t n_train, int model_kind,
+                         const float* model /* 9 */, const sift_mi_guided_params* params, sift_mi_match* out,
+                         size_t cap, size_t* n_matches);
+/* Diagnostic: the 128 x 128 tiles the guided calls covered and the waves (four
+ * per tile) that left at the cull (SIFT_MI_PATH_GUIDED_CULL); cumulative,
+ * reset by sift_mi_reset_stats. */
+int sift_mi_guided_counters(sift_mi_ctx* ctx, uint64_t* tiles, uint64_t* culled_waves);
+
 /* ---- the input step before the path ---------------
  * Baseline (SOF0/SOF1) Huffman JPEG, 1 or 3 components -> 8-bit luma, with
  * the arithmetic of the reference's decode: image 0.25.2 `image::open` /
@@ -471,7 +540,10 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        changed): sift_mi_verify_pairs_device, sift_mi_verify_matches
  *        (RANSAC homography + inlier refit of matched pairs);
  *        sift_mi_verify_pairs_epipolar_device, sift_mi_verify_matches_epipolar
- *        (RANSAC fundamental matrix + inlier refit; sift_mi_fundamental).
+ *        (RANSAC fundamental matrix + inlier refit; sift_mi_fundamental);
+ *        sift_mi_match_pairs_guided_device, sift_mi_match_guided,
+ *        sift_mi_guided_counters (guided matching under the verified models;
+ *        sift_mi_model_kind, sift_mi_guided_params), SIFT_MI_PATH_GUIDED_CULL.
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

@@ -8,7 +8,7 @@ from .sift import (  # noqa: F401
     DESCRIPTOR_SIZE, Context, ImageprocProcessing, KeyPoint, OpenCVProcessing, PrecomputedImages, Processing,
     ResultBuffers,
     SiftResult, compute_descriptor, decode_jpeg, default_context, jpeg_dims, key_fields, match_descriptors,
-    match_frames, match_neighbors, match_pairs_device,
+    match_frames, match_frames_guided, match_guided, match_neighbors, match_pairs_device, match_pairs_guided_device,
     precompute_images, sift,
     sift_with_precomputed,
     sift_with_processing, stable_sort_xy_size, verify_frames, verify_matches, verify_pairs_device)

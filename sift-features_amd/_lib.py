@@ -25,6 +25,7 @@ EXPORTS = [
     "sift_mi_match_neighbors", "sift_mi_match_ratio", "sift_mi_match_pairs_device",
     "sift_mi_verify_pairs_device", "sift_mi_verify_matches",
     "sift_mi_verify_pairs_epipolar_device", "sift_mi_verify_matches_epipolar",
+    "sift_mi_match_pairs_guided_device", "sift_mi_match_guided", "sift_mi_guided_counters",
     "sift_mi_decode_jpeg", "sift_mi_decode_jpeg_batch", "sift_mi_get_stats",
     "sift_mi_reset_stats",
     "sift_mi_version", "sift_mi_last_error",
@@ -70,6 +71,15 @@ class Fundamental(ctypes.Structure):
     """include/sift_mi.h sift_mi_fundamental (f all 0, best_hypothesis -1: no model; rank 2 iff refits >= 1)."""
     _fields_ = [("f", ctypes.c_float * 9), ("n_matches", ctypes.c_uint32), ("n_inliers", ctypes.c_uint32),
                 ("best_hypothesis", ctypes.c_int32), ("refits", ctypes.c_uint32)]
+
+
+class GuidedParams(ctypes.Structure):
+    """include/sift_mi.h sift_mi_guided_params."""
+    _fields_ = [("threshold", ctypes.c_float), ("ratio", ctypes.c_float), ("max_distance", ctypes.c_float),
+                ("cross_check", ctypes.c_int)]
+
+
+MODEL_KINDS = {"homography": 0, "fundamental": 1}  # include/sift_mi.h sift_mi_model_kind
 
 
 class Stats(ctypes.Structure):
@@ -146,6 +156,9 @@ def lib():
         "sift_mi_verify_matches": [vp, vp, sz, vp, sz, vp, sz, P(RansacParams), vp, vp],
         "sift_mi_verify_pairs_epipolar_device": [vp, vp, P(sz), u32, vp, u32, vp, P(sz), P(RansacParams), vp, vp],
         "sift_mi_verify_matches_epipolar": [vp, vp, sz, vp, sz, vp, sz, P(RansacParams), vp, vp],
+        "sift_mi_match_pairs_guided_device": [vp, vp, vp, P(sz), u32, vp, u32, i32, vp, P(GuidedParams), vp, sz, P(sz)],
+        "sift_mi_match_guided": [vp, vp, vp, sz, vp, vp, sz, i32, vp, P(GuidedParams), vp, sz, P(sz)],
+        "sift_mi_guided_counters": [vp, P(u64), P(u64)],
         "sift_mi_jpeg_dims": [vp, sz, P(u32), P(u32)],
         "sift_mi_decode_jpeg": [vp, vp, sz, vp, sz, i32],
         "sift_mi_decode_jpeg_batch": [vp, P(vp), P(sz), u32, vp, sz, sz, i32],

@@ -182,22 +182,29 @@ int check_ratio(float ratio) {
     return 0;
 }
 
-// The segmented matcher on device rows d_desc: validates the segments and
-// pairs, runs the launch sequence on the context stream and leaves, per
-// (pair, query) slot in pair order, the kept train index (-1: no match) and
-// distance in c->match.h_tix / h_dist (with `neighbors`, both neighbours in
-// h_nb_idx / h_nb_dist), synchronised.  P[p].qoff = pair p's first slot.
-int match_pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets, uint32_t n_segs,
-                    const sift_mi_seg_pair* pairs, uint32_t n_pairs, float ratio, int cross_check, bool neighbors,
-                    std::vector<MatchPair>& P) {
+// What a segmented match call covers: the arena rows of its segments, the
+// (pair, query) slots, (pair, train) columns and 128 x 128 tiles of its pairs,
+// and the words of its device table (the pairs, then the norm blocks).
+struct MatchPlan {
+    size_t row_base = 0, n_rows = 0, slots = 0, cols = 0, tiles = 0, n_blocks = 0, pair_words = 0, words = 0;
+};
+
+// Validates the segments and pairs of a segmented match call on device rows
+// d_desc and fills P (P[p].qoff = pair p's first slot) and L.  With at least
+// one slot it also fills the host table and grows the buffers every such call
+// uses; nothing has run on the device yet.
+int match_pairs_plan(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets, uint32_t n_segs,
+                     const sift_mi_seg_pair* pairs, uint32_t n_pairs, std::vector<MatchPair>& P, MatchPlan& L) {
     constexpr size_t kMax = 0x7fffffff;
     if (((uintptr_t)d_desc & 15) != 0) return fail(SIFT_MI_EINVAL, "d_desc must be 16-byte aligned");
     for (uint32_t s = 0; s < n_segs; s++) {
         if (offsets[s + 1] < offsets[s]) return fail(SIFT_MI_EINVAL, "offsets decrease");
         if (offsets[s + 1] - offsets[s] > kMax) return fail(SIFT_MI_EINVAL, "segment longer than 2^31 - 1 rows");
     }
-    const size_t row_base = offsets[0], n_rows = offsets[n_segs] - offsets[0];
-    if (n_rows > kMax) return fail(SIFT_MI_EINVAL, "segments sum to more than 2^31 - 1 rows");
+    L = MatchPlan{};
+    L.row_base = offsets[0];
+    L.n_rows = offsets[n_segs] - offsets[0];
+    if (L.n_rows > kMax) return fail(SIFT_MI_EINVAL, "segments sum to more than 2^31 - 1 rows");
     P.assign((size_t)n_pairs + 1, MatchPair{});
     std::vector<char> used(n_segs, 0);
     size_t slots = 0, cols = 0, tiles = 0;
@@ -205,9 +212,9 @@ int match_pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets
         const uint32_t qs = pairs[p].query_seg, ts = pairs[p].train_seg;
         if (qs >= n_segs || ts >= n_segs) return fail(SIFT_MI_EINVAL, "pair names a segment >= n_segs");
         MatchPair& m = P[p];
-        m.qrow0 = (uint32_t)(offsets[qs] - row_base);
+        m.qrow0 = (uint32_t)(offsets[qs] - L.row_base);
         m.nq = (uint32_t)(offsets[qs + 1] - offsets[qs]);
-        m.trow0 = (uint32_t)(offsets[ts] - row_base);
+        m.trow0 = (uint32_t)(offsets[ts] - L.row_base);
         m.nt = (uint32_t)(offsets[ts + 1] - offsets[ts]);
         m.qoff = (uint32_t)slots;
         m.toff = (uint32_t)cols;
@@ -224,28 +231,30 @@ int match_pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets
     P[n_pairs].qoff = (uint32_t)slots;
     P[n_pairs].toff = (uint32_t)cols;
     P[n_pairs].tile0 = (uint32_t)tiles;
+    L.slots = slots;
+    L.cols = cols;
+    L.tiles = tiles;
     if (slots == 0) return 0;
 
     CHK(set_device(c));
     MatchScratch& M = c->match;
     // table: the pairs, then the 256-row blocks of the segments in use (their norms)
-    const size_t pair_words = P.size() * (sizeof(MatchPair) / 4);
-    size_t n_blocks = 0;
+    L.pair_words = P.size() * (sizeof(MatchPair) / 4);
     for (uint32_t s = 0; s < n_segs; s++)
-        if (used[s]) n_blocks += (offsets[s + 1] - offsets[s] + 255) / 256;
-    const size_t words = pair_words + 2 * n_blocks;
-    CHK(pool(M.h_table, words));
-    std::memcpy(M.h_table.p, P.data(), pair_words * 4);
-    uint32_t* blk = M.h_table.p + pair_words;
+        if (used[s]) L.n_blocks += (offsets[s + 1] - offsets[s] + 255) / 256;
+    L.words = L.pair_words + 2 * L.n_blocks;
+    CHK(pool(M.h_table, L.words));
+    std::memcpy(M.h_table.p, P.data(), L.pair_words * 4);
+    uint32_t* blk = M.h_table.p + L.pair_words;
     for (uint32_t s = 0; s < n_segs; s++) {
         if (!used[s]) continue;
         for (size_t r = offsets[s]; r < offsets[s + 1]; r += 256) {
-            *blk++ = (uint32_t)(r - row_base);
+            *blk++ = (uint32_t)(r - L.row_base);
             *blk++ = (uint32_t)std::min<size_t>(256, offsets[s + 1] - r);
         }
     }
-    CHK(pool(M.table, words));
-    CHK(pool(M.nrm, n_rows));
+    CHK(pool(M.table, L.words));
+    CHK(pool(M.nrm, L.n_rows));
     CHK(pool(M.best, slots));
     CHK(pool(M.second, slots));
     CHK(pool(M.col, cols));
@@ -253,22 +262,25 @@ int match_pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets
     CHK(pool(M.dist, slots));
     CHK(pool(M.h_tix, slots));
     CHK(pool(M.h_dist, slots));
-    if (neighbors) {
-        CHK(pool(M.nb_idx, 2 * slots));
-        CHK(pool(M.nb_dist, 2 * slots));
-        CHK(pool(M.h_nb_idx, 2 * slots));
-        CHK(pool(M.h_nb_dist, 2 * slots));
-    }
     if (!M.t0) HIPCHK(hipEventCreate(&M.t0));
     if (!M.t1) HIPCHK(hipEventCreate(&M.t1));
+    return 0;
+}
+
+// Runs a planned call on the context stream: uploads the table, `launch`es the
+// kernels between the two events of sift_mi_stats.match_ms and leaves, per
+// (pair, query) slot in pair order, the kept train index (-1: no match) and
+// distance in c->match.h_tix / h_dist (with `neighbors`, both neighbours in
+// h_nb_idx / h_nb_dist; with `guided`, the culled waves in h_culled),
+// synchronised.
+template <class Launch>
+int match_pairs_execute(sift_mi_ctx* c, const MatchPlan& L, bool neighbors, bool guided, Launch&& launch) {
+    MatchScratch& M = c->match;
     hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(M.table.p, M.h_table.p, words * 4, hipMemcpyHostToDevice, st));
+    const size_t slots = L.slots;
+    HIPCHK(hipMemcpyAsync(M.table.p, M.h_table.p, L.words * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(M.t0, st));
-    launch_match_pairs(d_desc + row_base * kDescSize, reinterpret_cast<const MatchPair*>(M.table.p), (int)n_pairs,
-                       (uint32_t)tiles, (uint32_t)slots, (uint32_t)cols,
-                       reinterpret_cast<const uint2*>(M.table.p + pair_words), (uint32_t)n_blocks, cross_check ? 1 : 0,
-                       ratio, M.nrm.p, M.best.p, M.second.p, M.col.p, M.tix.p, M.dist.p,
-                       neighbors ? M.nb_idx.p : nullptr, neighbors ? M.nb_dist.p : nullptr, st);
+    launch(st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(M.t1, st));
     HIPCHK(hipMemcpyAsync(M.h_tix.p, M.tix.p, slots * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -277,10 +289,97 @@ int match_pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets
         HIPCHK(hipMemcpyAsync(M.h_nb_idx.p, M.nb_idx.p, 2 * slots * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(M.h_nb_dist.p, M.nb_dist.p, 2 * slots * sizeof(float), hipMemcpyDeviceToHost, st));
     }
+    if (guided)
+        HIPCHK(hipMemcpyAsync(M.h_culled.p, M.n_culled.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, M.t0, M.t1) == hipSuccess) c->stats.match_ms += ms;
-    c->stats.match_tiles += tiles;
+    return 0;
+}
+
+// The segmented matcher on device rows d_desc (match_pairs_plan, then
+// launch_match_pairs through match_pairs_execute).
+int match_pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const size_t* offsets, uint32_t n_segs,
+                    const sift_mi_seg_pair* pairs, uint32_t n_pairs, float ratio, int cross_check, bool neighbors,
+                    std::vector<MatchPair>& P) {
+    MatchPlan L;
+    CHK(match_pairs_plan(c, d_desc, offsets, n_segs, pairs, n_pairs, P, L));
+    if (L.slots == 0) return 0;
+    MatchScratch& M = c->match;
+    if (neighbors) {
+        CHK(pool(M.nb_idx, 2 * L.slots));
+        CHK(pool(M.nb_dist, 2 * L.slots));
+        CHK(pool(M.h_nb_idx, 2 * L.slots));
+        CHK(pool(M.h_nb_dist, 2 * L.slots));
+    }
+    CHK(match_pairs_execute(c, L, neighbors, false, [&](hipStream_t st) {
+        launch_match_pairs(d_desc + L.row_base * kDescSize, reinterpret_cast<const MatchPair*>(M.table.p), (int)n_pairs,
+                           (uint32_t)L.tiles, (uint32_t)L.slots, (uint32_t)L.cols,
+                           reinterpret_cast<const uint2*>(M.table.p + L.pair_words), (uint32_t)L.n_blocks,
+                           cross_check ? 1 : 0, ratio, M.nrm.p, M.best.p, M.second.p, M.col.p, M.tix.p, M.dist.p,
+                           neighbors ? M.nb_idx.p : nullptr, neighbors ? M.nb_dist.p : nullptr, st);
+    }));
+    c->stats.match_tiles += L.tiles;
+    return 0;
+}
+
+int check_guided(int model_kind, const sift_mi_guided_params* p, const float* models, size_t n_pairs) {
+    if (model_kind != SIFT_MI_MODEL_HOMOGRAPHY && model_kind != SIFT_MI_MODEL_FUNDAMENTAL)
+        return fail(SIFT_MI_EINVAL, "unknown model kind");
+    if (!(std::isfinite(p->threshold) && p->threshold > 0.0f))
+        return fail(SIFT_MI_EINVAL, "threshold must be finite and > 0");
+    CHK(check_ratio(p->ratio));
+    if (!(p->max_distance >= 0.0f)) return fail(SIFT_MI_EINVAL, "max_distance must be 0 (no cap) or > 0");
+    for (size_t i = 0; i < n_pairs * 9; i++)
+        if (!std::isfinite(models[i])) return fail(SIFT_MI_EINVAL, "model entry not finite");
+    return 0;
+}
+
+// The guided matcher on device rows d_desc and device keypoints d_kps of the
+// same arena (with d_kps null, the host keypoints h_query / h_train of its two
+// segments): every check on the host first, then match_pairs_run's sequence
+// with launch_match_pairs_guided.  models: n_pairs * 9 host f32.
+int match_guided_run(sift_mi_ctx* c, const uint8_t* d_desc, const OutKp* d_kps, const size_t* offsets, uint32_t n_segs,
+                     const sift_mi_seg_pair* pairs, uint32_t n_pairs, int model_kind, const float* models,
+                     const sift_mi_guided_params* prm, std::vector<MatchPair>& P, const OutKp* h_query = nullptr,
+                     const OutKp* h_train = nullptr) {
+    CHK(check_guided(model_kind, prm, models, n_pairs));
+    if (((uintptr_t)d_kps & 3) != 0) return fail(SIFT_MI_EINVAL, "d_kps must be 4-byte aligned");
+    MatchPlan L;
+    CHK(match_pairs_plan(c, d_desc, offsets, n_segs, pairs, n_pairs, P, L));
+    if (L.slots == 0) return 0;
+    MatchScratch& M = c->match;
+    const size_t n_models = (size_t)n_pairs * 9;
+    CHK(pool(M.h_models, n_models));
+    CHK(pool(M.models, n_models));
+    CHK(pool(M.qterm, L.slots));
+    CHK(pool(M.tterm, L.cols));
+    CHK(pool(M.culled, L.tiles));
+    CHK(pool(M.n_culled, 1));
+    CHK(pool(M.h_culled, 1));
+    hipStream_t st = c->stream;
+    if (!d_kps) {  // host keypoints (two segments) as the context's own arena
+        const size_t nq = offsets[1], nt = offsets[2] - offsets[1];
+        CHK(pool(M.kps, nq + nt));
+        if (nq) HIPCHK(hipMemcpyAsync(M.kps.p, h_query, nq * sizeof(OutKp), hipMemcpyHostToDevice, st));
+        if (nt) HIPCHK(hipMemcpyAsync(M.kps.p + nq, h_train, nt * sizeof(OutKp), hipMemcpyHostToDevice, st));
+        d_kps = M.kps.p;
+    }
+    std::memcpy(M.h_models.p, models, n_models * sizeof(float));
+    HIPCHK(hipMemcpyAsync(M.models.p, M.h_models.p, n_models * sizeof(float), hipMemcpyHostToDevice, st));
+    const int cull = c->opts.guided_cull;
+    CHK(match_pairs_execute(c, L, false, true, [&](hipStream_t s) {
+        launch_match_pairs_guided(d_desc + L.row_base * kDescSize, d_kps + L.row_base,
+                                  reinterpret_cast<const MatchPair*>(M.table.p), (int)n_pairs, (uint32_t)L.tiles,
+                                  (uint32_t)L.slots, (uint32_t)L.cols,
+                                  reinterpret_cast<const uint2*>(M.table.p + L.pair_words), (uint32_t)L.n_blocks,
+                                  model_kind == SIFT_MI_MODEL_FUNDAMENTAL, M.models.p, prm->threshold, cull,
+                                  prm->cross_check ? 1 : 0, prm->ratio, prm->max_distance, M.nrm.p, M.best.p,
+                                  M.second.p, M.col.p, M.qterm.p, M.tterm.p, M.culled.p, M.n_culled.p, M.tix.p,
+                                  M.dist.p, s);
+    }));
+    M.guided_tiles += L.tiles;
+    M.guided_culled += *M.h_culled.p;
     return 0;
 }
 
@@ -558,6 +657,7 @@ int sift_mi_set_path_option(sift_mi_ctx* c, int option, int value) {
         case SIFT_MI_PATH_BD_PAIR: if (value < 0 || value > 2) break; o.bd_pair = value; return 0;
         case SIFT_MI_PATH_BD_WAVES: if (value < 1024 || value > 65536) break; o.bd_waves = value; return 0;
         case SIFT_MI_PATH_CHUNK_MODE: if (value < 0 || value > 1) break; o.chunk_mode = value; return 0;
+        case SIFT_MI_PATH_GUIDED_CULL: if (!b) break; o.guided_cull = value; return 0;
         default: return fail(SIFT_MI_EINVAL, "unknown path option");
     }
     return fail(SIFT_MI_EINVAL, "path option value out of range");
@@ -874,6 +974,54 @@ int sift_mi_match_neighbors(sift_mi_ctx* c, const uint8_t* query, size_t nq, con
     });
 }
 
+// ---- guided matching under verified models (labelled extension; match_guided.hip)
+int sift_mi_match_pairs_guided_device(sift_mi_ctx* c, const uint8_t* d_desc, const sift_mi_keypoint* d_kps,
+                                      const size_t* offsets, uint32_t n_segs, const sift_mi_seg_pair* pairs,
+                                      uint32_t n_pairs, int model_kind, const float* models,
+                                      const sift_mi_guided_params* params, sift_mi_match* out, size_t cap,
+                                      size_t* pair_offsets) {
+    if (!c || !d_desc || !d_kps || !offsets || !pairs || !models || !params || !pair_offsets)
+        return fail(SIFT_MI_EINVAL, "null argument");
+    return match_guard([&]() -> int {
+        std::vector<MatchPair> P;
+        CHK(match_guided_run(c, d_desc, reinterpret_cast<const OutKp*>(d_kps), offsets, n_segs, pairs, n_pairs,
+                             model_kind, models, params, P));
+        return match_pairs_collect(c, P, out, cap, pair_offsets);
+    });
+}
+
+int sift_mi_match_guided(sift_mi_ctx* c, const uint8_t* query, const sift_mi_keypoint* query_kps, size_t nq,
+                         const uint8_t* train, const sift_mi_keypoint* train_kps, size_t nt, int model_kind,
+                         const float* model, const sift_mi_guided_params* params, sift_mi_match* out, size_t cap,
+                         size_t* n_matches) {
+    if (!c || !n_matches || !model || !params || (nq && (!query || !query_kps)) || (nt && (!train || !train_kps)))
+        return fail(SIFT_MI_EINVAL, "null argument");
+    if (nq > 0x7fffffff || nt > 0x7fffffff || nq + nt > 0x7fffffff)
+        return fail(SIFT_MI_EINVAL, "descriptor set too large");
+    *n_matches = 0;
+    return match_guard([&]() -> int {
+        CHK(check_guided(model_kind, params, model, 1));
+        if (nq == 0) return 0;
+        CHK(match_upload(c, query, nq, train, nt));
+        const size_t offsets[3] = {0, nq, nq + nt};
+        const sift_mi_seg_pair pair{0, 1};
+        std::vector<MatchPair> P;
+        CHK(match_guided_run(c, c->match.desc.p, nullptr, offsets, 2, &pair, 1, model_kind, model, params, P,
+                             reinterpret_cast<const OutKp*>(query_kps), reinterpret_cast<const OutKp*>(train_kps)));
+        size_t po[2] = {0, 0};
+        const int rc = match_pairs_collect(c, P, out, cap, po);
+        *n_matches = po[1];
+        return rc;
+    });
+}
+
+int sift_mi_guided_counters(sift_mi_ctx* c, uint64_t* tiles, uint64_t* culled_waves) {
+    if (!c || !tiles || !culled_waves) return fail(SIFT_MI_EINVAL, "null argument");
+    *tiles = c->match.guided_tiles;
+    *culled_waves = c->match.guided_culled;
+    return 0;
+}
+
 // ---- geometric verification (labelled extensions; verify.hip, verify_epipolar.hip)
 namespace {
 int verify_pairs_device(VerifyKind kind, sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets,
@@ -1014,6 +1162,7 @@ int sift_mi_get_stats(sift_mi_ctx* c, sift_mi_stats* out) {
 int sift_mi_reset_stats(sift_mi_ctx* c) {
     if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
     c->stats = sift_mi_stats{};
+    c->match.guided_tiles = c->match.guided_culled = 0;
     if (c->samples.p) {
         CHK(set_device(c));
         CHK(sync_lanes(c));

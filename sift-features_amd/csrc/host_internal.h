@@ -280,6 +280,15 @@ struct MatchScratch {
     DevBuf<float> dist, nb_dist;
     PinBuf<int> h_tix, h_nb_idx;
     PinBuf<float> h_dist, h_nb_dist;
+    // the guided matcher (sift_mi_match_pairs_guided_device, sift_mi_match_guided)
+    DevBuf<OutKp> kps;         // sift_mi_match_guided: [query keypoints | train keypoints]
+    DevBuf<float> models;      // per pair 9 f32
+    PinBuf<float> h_models;
+    DevBuf<float4> qterm, tterm;  // the gate's per (pair, query) / per (pair, train) terms
+    DevBuf<uint32_t> culled;      // per tile: one byte per wave, 1 where it left at the cull
+    DevBuf<unsigned long long> n_culled;
+    PinBuf<unsigned long long> h_culled;
+    uint64_t guided_tiles = 0, guided_culled = 0;  // sift_mi_guided_counters
     hipEvent_t t0 = nullptr, t1 = nullptr;  // around the kernels (sift_mi_stats.match_ms)
     ~MatchScratch() {
         if (t0) (void)hipEventDestroy(t0);

@@ -16,15 +16,12 @@
 // MFMA tiles, 8 k-steps); the tile's row / column minima are folded into
 // global per-query and per-train (d^2 << 32 | index) keys with 64-bit
 // atomicMin, which also gives the lowest-index tie break.
-#include "sift_common.h"
-#include "sift_kernels.h"
+#include "match_common.h"
 
 namespace siftmi {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ short u8_to_bf16(uint32_t v) {
     return (short)(__float_as_uint((float)v) >> 16);  // exact for 0..255
@@ -208,44 +205,8 @@ void launch_match(const uint8_t* q, int nq, const uint8_t* t, int nt, int cross_
 // else that reaches `second` is larger, so the final state is (g, s) for
 // every arrival order and every tiling.
 
-// Inside a wave the keys are 32 bits: (d^2 << 6 | the row's / column's index
-// within the wave's 64), d^2 < 2^23; an invalid row or column has kBadD2 added
-// to its d^2 (through its m), so its keys sort last and are >= kBadKey.
-constexpr int kBadD2 = 1 << 24;
-constexpr uint32_t kBadKey = (uint32_t)kBadD2 << 6;
-
-// Merge of two sorted key pairs (valid keys are distinct).
-__device__ __forceinline__ void merge2(uint32_t& lo, uint32_t& hi, uint32_t olo, uint32_t ohi) {
-    const uint32_t big = max(lo, olo);
-    lo = min(lo, olo);
-    hi = min(big, min(hi, ohi));
-}
-
-// One step of the transposing reduction over n rows held per lane: lanes with
-// bit m clear keep rows [0, n/2) and send [n/2, n) to lane ^ m, the others the
-// reverse; each lane leaves with n/2 rows merged over twice as many lanes.
-template <int N>
-__device__ __forceinline__ void fold_rows(uint32_t (&lo)[16], uint32_t (&hi)[16], int m, bool up) {
-#pragma unroll
-    for (int j = 0; j < N / 2; j++) {
-        const uint32_t klo = up ? lo[j + N / 2] : lo[j], khi = up ? hi[j + N / 2] : hi[j];
-        const uint32_t slo = up ? lo[j] : lo[j + N / 2], shi = up ? hi[j] : hi[j + N / 2];
-        lo[j] = klo;
-        hi[j] = khi;
-        merge2(lo[j], hi[j], __shfl_xor(slo, m), __shfl_xor(shi, m));
-    }
-}
-
-__device__ __forceinline__ int pair_of(const MatchPair* __restrict__ pairs, int n_pairs, uint32_t v, bool by_tile) {
-    // the last pair whose first tile (first query slot) is <= v
-    int lo = 0, hi = n_pairs;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((by_tile ? pairs[mid].tile0 : pairs[mid].qoff) <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+// The in-wave 32-bit keys, merge2 / fold_rows, pair_of and load_frag_i8 are in
+// match_common.h (the guided tile kernel of match_guided.hip uses them too).
 
 // Per row of the segments some pair uses, m = |row|^2 - 256 * sum(row) (the
 // row's part of d^2 in the biased i8 form, below); blocks[b] = (first arena
@@ -272,19 +233,6 @@ __global__ __launch_bounds__(256) void k_match_seg_norms(const uint8_t* __restri
             }
     }
     nrm[i] = (int)s2 - 256 * (int)s1;
-}
-
-// 16 consecutive u8 of one descriptor row, biased by -128 -> i8 MFMA fragment
-__device__ __forceinline__ i32x4 load_frag_i8(const uint8_t* __restrict__ base, int row, int n, int k0) {
-    i32x4 f = {0, 0, 0, 0};
-    if (row < n) {
-        const uint4 w = *reinterpret_cast<const uint4*>(base + (size_t)row * kDescSize + k0);
-        f[0] = (int)(w.x ^ 0x80808080u);
-        f[1] = (int)(w.y ^ 0x80808080u);
-        f[2] = (int)(w.z ^ 0x80808080u);
-        f[3] = (int)(w.w ^ 0x80808080u);
-    }
-    return f;
 }
 
 // (256, 3): with three waves per SIMD asked for, the accumulators stay in the
@@ -413,6 +361,9 @@ __global__ __launch_bounds__(256, 3) void k_match_seg_tiles(const uint8_t* __res
 // Per (pair, query): cross check as k_match_final, the ratio test
 // dist1 < ratio * dist2 (f32, one multiply; ratio == 0: none; no second
 // neighbour: rejected), and optionally both neighbours (knnMatch, k = 2).
+// The guided matcher (match_guided.hip) runs it with lone_passes (no second
+// neighbour: dist2 = +inf, the test passes) and max_distance > 0 (kept only if
+// dist1 <= max_distance); 0 / 0 is the unguided rule.
 __global__ __launch_bounds__(256) void k_match_seg_final(const MatchPair* __restrict__ pairs, int n_pairs,
                                                          uint32_t n_slots,
                                                          const unsigned long long* __restrict__ best,
@@ -420,7 +371,8 @@ __global__ __launch_bounds__(256) void k_match_seg_final(const MatchPair* __rest
                                                          const unsigned long long* __restrict__ col_best,
                                                          int cross_check, float ratio, int* __restrict__ train_idx,
                                                          float* __restrict__ dist, int* __restrict__ nb_idx,
-                                                         float* __restrict__ nb_dist) {
+                                                         float* __restrict__ nb_dist, float max_distance,
+                                                         int lone_passes) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_slots) return;
     const MatchPair P = pairs[pair_of(pairs, n_pairs, i, false)];
@@ -433,7 +385,8 @@ __global__ __launch_bounds__(256) void k_match_seg_final(const MatchPair* __rest
     const float d2 = has2 ? sqrtf((float)(uint32_t)(sb >> 32)) : INFINITY;
     bool keep = has1;
     if (keep && cross_check) keep = (int)(uint32_t)col_best[P.toff + (uint32_t)t1] == qi;
-    if (keep && ratio > 0.0f) keep = has2 && d1 < ratio * d2;
+    if (keep && ratio > 0.0f) keep = (has2 || lone_passes) && d1 < ratio * d2;
+    if (keep && max_distance > 0.0f) keep = d1 <= max_distance;
     train_idx[i] = keep ? t1 : -1;
     dist[i] = keep ? d1 : 0.0f;
     if (nb_idx) {
@@ -444,22 +397,37 @@ __global__ __launch_bounds__(256) void k_match_seg_final(const MatchPair* __rest
     }
 }
 
+void launch_match_seg_prepare(const uint8_t* d, uint32_t n_slots, uint32_t n_cols, const uint2* norm_blocks,
+                              uint32_t n_norm_blocks, int* nrm, unsigned long long* best, unsigned long long* second,
+                              unsigned long long* col_best, hipStream_t st) {
+    (void)hipMemsetAsync(best, 0xff, (size_t)n_slots * 8, st);
+    (void)hipMemsetAsync(second, 0xff, (size_t)n_slots * 8, st);
+    if (n_cols) (void)hipMemsetAsync(col_best, 0xff, (size_t)n_cols * 8, st);
+    if (n_norm_blocks)
+        hipLaunchKernelGGL(k_match_seg_norms, dim3(n_norm_blocks), dim3(256), 0, st, d, norm_blocks, nrm);
+}
+
+void launch_match_seg_final(const MatchPair* pairs, int n_pairs, uint32_t n_slots, const unsigned long long* best,
+                            const unsigned long long* second, const unsigned long long* col_best, int cross_check,
+                            float ratio, float max_distance, int lone_passes, int* train_idx, float* dist, int* nb_idx,
+                            float* nb_dist, hipStream_t st) {
+    hipLaunchKernelGGL(k_match_seg_final, dim3((n_slots + 255) / 256), dim3(256), 0, st, pairs, n_pairs, n_slots, best,
+                       second, col_best, cross_check, ratio, train_idx, dist, nb_idx, nb_dist, max_distance,
+                       lone_passes);
+}
+
 void launch_match_pairs(const uint8_t* d, const MatchPair* pairs, int n_pairs, uint32_t n_tiles, uint32_t n_slots,
                         uint32_t n_cols, const uint2* norm_blocks, uint32_t n_norm_blocks, int cross_check,
                         float ratio, int* nrm, unsigned long long* best, unsigned long long* second,
                         unsigned long long* col_best, int* train_idx, float* dist, int* nb_idx, float* nb_dist,
                         hipStream_t st) {
     if (n_slots == 0) return;
-    (void)hipMemsetAsync(best, 0xff, (size_t)n_slots * 8, st);
-    (void)hipMemsetAsync(second, 0xff, (size_t)n_slots * 8, st);
-    if (n_cols) (void)hipMemsetAsync(col_best, 0xff, (size_t)n_cols * 8, st);
-    if (n_norm_blocks)
-        hipLaunchKernelGGL(k_match_seg_norms, dim3(n_norm_blocks), dim3(256), 0, st, d, norm_blocks, nrm);
+    launch_match_seg_prepare(d, n_slots, n_cols, norm_blocks, n_norm_blocks, nrm, best, second, col_best, st);
     if (n_tiles)
         hipLaunchKernelGGL(k_match_seg_tiles, dim3(n_tiles), dim3(256), 0, st, d, nrm, pairs, n_pairs, best, second,
                            col_best);
-    hipLaunchKernelGGL(k_match_seg_final, dim3((n_slots + 255) / 256), dim3(256), 0, st, pairs, n_pairs, n_slots, best,
-                       second, col_best, cross_check, ratio, train_idx, dist, nb_idx, nb_dist);
+    launch_match_seg_final(pairs, n_pairs, n_slots, best, second, col_best, cross_check, ratio, 0.0f, 0, train_idx,
+                           dist, nb_idx, nb_dist, st);
 }
 
 }  // namespace siftmi

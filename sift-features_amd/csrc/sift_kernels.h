@@ -64,6 +64,7 @@ struct PathOpts {
                            // one-column k_blur_detect (2, once a 4-row loop form of the pair kernel, is read as 1)
     int bd_waves = 8192;   // k_blur_detect_pair: fewest waves per launch at the chosen row segments
     int chunk_mode = 1;    // automatic chunking (SIFT_MI_PATH_CHUNK_MODE)
+    int guided_cull = 1;   // guided matcher: a wave whose 64 x 64 block admits nothing skips its loads and MFMAs
     int onesweep = 0;      // emission-order sorts with rocprim's Onesweep: 1 always, 0 never (the
                            // library default path), 2 for bounds >= kOnesweepMinKeys
 };
@@ -317,6 +318,30 @@ void launch_match_pairs(const uint8_t* d, const MatchPair* pairs, int n_pairs, u
                         float ratio, int* nrm, unsigned long long* best, unsigned long long* second,
                         unsigned long long* col_best, int* train_idx, float* dist, int* nb_idx, float* nb_dist,
                         hipStream_t st);
+// The steps around its tile kernel, shared with the guided matcher: the
+// memsets of best / second / col_best and the norms, and the final pass
+// (max_distance == 0 and lone_passes == 0: the unguided rule; k_match_seg_final).
+void launch_match_seg_prepare(const uint8_t* d, uint32_t n_slots, uint32_t n_cols, const uint2* norm_blocks,
+                              uint32_t n_norm_blocks, int* nrm, unsigned long long* best, unsigned long long* second,
+                              unsigned long long* col_best, hipStream_t st);
+void launch_match_seg_final(const MatchPair* pairs, int n_pairs, uint32_t n_slots, const unsigned long long* best,
+                            const unsigned long long* second, const unsigned long long* col_best, int cross_check,
+                            float ratio, float max_distance, int lone_passes, int* train_idx, float* dist, int* nb_idx,
+                            float* nb_dist, hipStream_t st);
+
+// match_guided.hip
+// launch_match_pairs over the elements the pairs' models admit (LABELLED
+// EXTENSION; tests/guided_ref.py is the definition).  kps: the keypoints of the
+// arena's rows; models[n_pairs * 9]: H or F per pair (device memory); qterm
+// [n_slots], tterm[n_cols], culled[n_tiles] are scratch; *n_culled receives
+// the waves that left at the cull (cull != 0).
+void launch_match_pairs_guided(const uint8_t* d, const OutKp* kps, const MatchPair* pairs, int n_pairs,
+                               uint32_t n_tiles, uint32_t n_slots, uint32_t n_cols, const uint2* norm_blocks,
+                               uint32_t n_norm_blocks, bool fundamental, const float* models, float thr, int cull,
+                               int cross_check, float ratio, float max_distance, int* nrm, unsigned long long* best,
+                               unsigned long long* second, unsigned long long* col_best, float4* qterm, float4* tterm,
+                               uint32_t* culled, unsigned long long* n_culled, int* train_idx, float* dist,
+                               hipStream_t st);
 
 // verify.hip
 // RANSAC homography + inlier refit of matched pairs (LABELLED EXTENSION;

@@ -278,7 +278,7 @@ class Context:
                     "band_drift": (8, 24), "bound_shrink": (9, 1),
                     "large_first": (11, 1),
                     "onesweep": (12, 0), "bd_pair": (13, 1), "bd_waves": (14, 8192),
-                    "chunk_mode": (15, 1)}
+                    "chunk_mode": (15, 1), "guided_cull": (16, 1)}
 
     def set_path_option(self, name, value):
         """One kernel-path switch (sift_mi_set_path_option), e.g.
@@ -494,6 +494,97 @@ class Context:
         check(call(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t), rec.ctypes.data, int(po[-1]),
                    ctypes.byref(prm), ctypes.byref(out), mask.ctypes.data))
         return self._verify_result(out, mask[:po[-1]])
+
+    # -- guided matching (LABELLED EXTENSION: not in the crate) ----------------
+    @staticmethod
+    def _guided(threshold, ratio, max_distance, cross_check, model):
+        if model not in _lib.MODEL_KINDS:
+            raise ValueError(f"model must be 'homography' or 'fundamental', not {model!r}")
+        return _lib.MODEL_KINDS[model], _lib.GuidedParams(float(threshold), float(ratio or 0.0),
+                                                          float(max_distance or 0.0), 1 if cross_check else 0)
+
+    @staticmethod
+    def _model_array(models):
+        """(H, mask, info) tuples of verify_frames or bare 3 x 3 arrays -> (n, 9) f32."""
+        rows = [np.asarray(m[0] if isinstance(m, tuple) else m, np.float32).reshape(9) for m in models]
+        return np.ascontiguousarray(np.stack(rows) if rows else np.zeros((0, 9), np.float32))
+
+    def match_pairs_guided_device(self, d_desc_ptr, d_kps_ptr, offsets, pairs, models, threshold=3.0,
+                                  model="homography", ratio=None, max_distance=None, cross_check=True):
+        """LABELLED EXTENSION: match_pairs_device again, a query keypoint
+        competing only for the train keypoints its pair's model admits
+        (sift_mi_match_pairs_guided_device; the rule is tests/guided_ref.py's).
+        d_kps_ptr: device pointer of the keypoints of the same rows;
+        models: per pair the (H, mask, info) tuple of verify_pairs_device or a
+        bare 3 x 3 array (H, or F with model="fundamental"); `threshold` as
+        the verification read it.  Admissible = the verification's own inlier
+        test on (query keypoint, train keypoint).  Nearest, second nearest
+        and the cross check run over the admissible candidates only; with
+        `ratio` a query with a single admissible candidate PASSES (its second
+        distance is +inf; the unguided ratio test rejects it), and
+        `max_distance` keeps a query only if its distance is <= it.  A pair
+        with an all-zero model (no model) gets no matches.  Returns one
+        (query_idx, train_idx, distance) triple per pair."""
+        kind, prm = self._guided(threshold, ratio, max_distance, cross_check, model)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
+            raise ValueError("offsets: n_segs + 1 non-negative row numbers")
+        pr = [(int(a), int(b)) for a, b in pairs]
+        g = self._model_array(models)
+        if len(g) != len(pr):
+            raise ValueError("one model per pair")
+        c_offs = (ctypes.c_size_t * len(offs))(*[int(v) for v in offs])
+        c_pairs = (_lib.SegPair * max(len(pr), 1))(*[_lib.SegPair(a, b) for a, b in pr])
+        n_seg = len(offs) - 1
+        cap = sum(int(offs[a + 1] - offs[a]) for a, _ in pr if 0 <= a < n_seg and offs[a + 1] >= offs[a])
+        out = (_lib.Match * max(cap, 1))()
+        po = (ctypes.c_size_t * (len(pr) + 1))()
+        g = g if len(g) else np.zeros((1, 9), np.float32)
+        check(lib().sift_mi_match_pairs_guided_device(self._h, ctypes.c_void_p(d_desc_ptr), ctypes.c_void_p(d_kps_ptr),
+                                                      c_offs, n_seg, c_pairs, len(pr), kind, g.ctypes.data,
+                                                      ctypes.byref(prm), out, cap, po))
+        a = np.ctypeslib.as_array(out)
+        return [_match_arrays(a, po[p], po[p + 1]) for p in range(len(pr))]
+
+    def match_frames_guided(self, offsets, pairs, models, threshold=3.0, model="homography", ratio=None,
+                            max_distance=None, cross_check=True):
+        """match_pairs_guided_device on the keypoints and descriptors the last
+        sift_batch_device(..., fetch=False) left in HBM, e.g. with what
+        verify_frames(offsets, pairs, ...) returned as `models`."""
+        d_kps, d_desc, n = self.device_results()
+        if int(offsets[-1]) > n:
+            raise ValueError("offsets reach beyond the device results")
+        return self.match_pairs_guided_device(d_desc, d_kps, offsets, pairs, models, threshold, model, ratio,
+                                              max_distance, cross_check)
+
+    def match_guided(self, desc_q, kps_q, desc_t, kps_t, model_matrix, threshold=3.0, model="homography", ratio=None,
+                     max_distance=None, cross_check=True):
+        """The one-pair form on host arrays (sift_mi_match_guided): (n, 128) u8
+        descriptors and (n, 5) f32 keypoint arrays of the query and the train
+        image, one 3 x 3 model (or a verify_matches tuple).  Returns
+        (query_idx, train_idx, distance)."""
+        kind, prm = self._guided(threshold, ratio, max_distance, cross_check, model)
+        q = np.ascontiguousarray(desc_q, dtype=np.uint8).reshape(-1, DESCRIPTOR_SIZE)
+        t = np.ascontiguousarray(desc_t, dtype=np.uint8).reshape(-1, DESCRIPTOR_SIZE)
+        kq = np.ascontiguousarray(kps_q, dtype=np.float32).reshape(-1, 5)
+        kt = np.ascontiguousarray(kps_t, dtype=np.float32).reshape(-1, 5)
+        if len(kq) != len(q) or len(kt) != len(t):
+            raise ValueError("one keypoint row per descriptor row")
+        g = self._model_array([model_matrix])
+        out = (_lib.Match * max(len(q), 1))()
+        n = ctypes.c_size_t()
+        check(lib().sift_mi_match_guided(self._h, q.ctypes.data, kq.ctypes.data, len(q), t.ctypes.data, kt.ctypes.data,
+                                         len(t), kind, g.ctypes.data, ctypes.byref(prm), out, len(q), ctypes.byref(n)))
+        return _match_arrays(np.ctypeslib.as_array(out), 0, n.value)
+
+    def guided_counters(self):
+        """{"tiles", "culled_waves"} of the guided calls since the last
+        reset_stats(): the 128 x 128 tiles they covered and the waves (four
+        per tile) that skipped their block because the model admits none of
+        it (sift_mi_guided_counters; path option "guided_cull")."""
+        tiles, culled = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().sift_mi_guided_counters(self._h, ctypes.byref(tiles), ctypes.byref(culled)))
+        return {"tiles": tiles.value, "culled_waves": culled.value}
 
     # -- the input step (SURVEY.md 8(f) row 2) ------------------------------
     def decode_jpeg(self, data):
@@ -713,6 +804,28 @@ def verify_frames(offsets, pairs, matches, threshold=3.0, iterations=1024, seed=
 def verify_matches(kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2, model="homography"):
     """LABELLED EXTENSION: Context.verify_matches on the default context."""
     return default_context().verify_matches(kps_q, kps_t, matches, threshold, iterations, seed, refit_rounds, model)
+
+
+def match_pairs_guided_device(d_desc_ptr, d_kps_ptr, offsets, pairs, models, threshold=3.0, model="homography",
+                              ratio=None, max_distance=None, cross_check=True):
+    """LABELLED EXTENSION: Context.match_pairs_guided_device on the default context."""
+    return default_context().match_pairs_guided_device(d_desc_ptr, d_kps_ptr, offsets, pairs, models, threshold,
+                                                       model, ratio, max_distance, cross_check)
+
+
+def match_frames_guided(offsets, pairs, models, threshold=3.0, model="homography", ratio=None, max_distance=None,
+                        cross_check=True):
+    """LABELLED EXTENSION: Context.match_frames_guided on the default context
+    (its last sift_batch_device(..., fetch=False) results)."""
+    return default_context().match_frames_guided(offsets, pairs, models, threshold, model, ratio, max_distance,
+                                                 cross_check)
+
+
+def match_guided(desc_q, kps_q, desc_t, kps_t, model_matrix, threshold=3.0, model="homography", ratio=None,
+                 max_distance=None, cross_check=True):
+    """LABELLED EXTENSION: Context.match_guided on the default context."""
+    return default_context().match_guided(desc_q, kps_q, desc_t, kps_t, model_matrix, threshold, model, ratio,
+                                          max_distance, cross_check)
 
 
 def stable_sort_xy_size(keypoints_array):

@@ -2,7 +2,7 @@
 MI355X path.
 
     python sift-features_amd/sift_match.py <a.jpg> <b.jpg> [--ratio R] [--verify [THR]]
-                                           [--model homography|fundamental]
+                                           [--model homography|fundamental] [--guided]
                                            [--processing opencv|imageproc] [--device N]
 
 examples/sift-match.rs:30-35, :87-97 opens two images, runs `sift()` on each and
@@ -18,6 +18,10 @@ RANSAC homography to the matches (verify.hip, the defaults of
 Context.verify_matches) and prints a fourth line with its inlier count;
 with `--model fundamental` (only read with --verify) it fits a RANSAC
 fundamental matrix instead (verify_epipolar.hip; THR is the Sampson distance).
+`--guided` (only read with --verify), a further labelled extension, matches
+the pair again under the fitted model (match_guided.hip, the defaults of
+Context.match_guided: cross check, no ratio test, no distance cap, the
+verification's threshold) and prints a fifth line with the guided match count.
 Exits non-zero (with the library's error) when the HIP library or
 the device is missing: there is no CPU fallback.
 """
@@ -36,6 +40,7 @@ def main(argv=None):
     ap.add_argument("--ratio", type=float, default=None)
     ap.add_argument("--verify", type=float, nargs="?", const=3.0, default=None, metavar="THR")
     ap.add_argument("--model", choices=["homography", "fundamental"], default="homography")
+    ap.add_argument("--guided", action="store_true")
     ap.add_argument("--processing", choices=("imageproc", "opencv"), default="imageproc")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -51,8 +56,11 @@ def main(argv=None):
         res_a, res_b = (ctx.sift_jpeg(d) for d in datas)
         qi, ti, dist = ctx.match_descriptors(res_b.descriptors, res_a.descriptors, cross_check=True, ratio=a.ratio)
         if a.verify is not None:
-            _, _, info = ctx.verify_matches(res_b.keypoints_array, res_a.keypoints_array, (qi, ti, dist),
+            g, _, info = ctx.verify_matches(res_b.keypoints_array, res_a.keypoints_array, (qi, ti, dist),
                                             threshold=a.verify, model=a.model)
+            if a.guided:
+                guided = ctx.match_guided(res_b.descriptors, res_b.keypoints_array, res_a.descriptors,
+                                          res_a.keypoints_array, g, threshold=a.verify, model=a.model)
     finally:
         ctx.close()
     print(f"{len(res_a)} keypoints")
@@ -60,6 +68,8 @@ def main(argv=None):
     print(f"{len(qi)} matches" + (f" (ratio {a.ratio:g})" if a.ratio is not None else ""))
     if a.verify is not None:
         print(f"{info['n_inliers']} inliers ({a.model}, threshold {a.verify:g})")
+        if a.guided:
+            print(f"{len(guided[0])} guided matches")
     return 0
 
 
