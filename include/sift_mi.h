@@ -459,6 +459,52 @@ int sift_mi_match_guided(sift_mi_ctx* ctx, const uint8_t* query, const sift_mi_k
  * reset by sift_mi_reset_stats. */
 int sift_mi_guided_counters(sift_mi_ctx* ctx, uint64_t* tiles, uint64_t* culled_waves);
 
+/* ---- feature tracks (LABELLED EXTENSION: the crate has nothing like it) ----
+ * Links the kept matches of the pairs into tracks: the connected components
+ * of the graph whose nodes are the arena rows [offsets[0], offsets[n_segs])
+ * and whose edges join row offsets[query_seg] + query_idx to row
+ * offsets[train_seg] + train_idx for every match m of pair p, m in
+ * [pair_offsets[p], pair_offsets[p + 1]), with keep[m] != 0 (keep null: every
+ * match; the verification's inlier mask goes in unchanged).  The rule is
+ * tests/tracks_ref.py's; every output is integer-exact.  A component's label
+ * is its smallest row; it is in conflict when two of its rows lie in one
+ * segment; it is a track when it has at least min_length (>= 2) rows and,
+ * with drop_conflicts != 0, is not in conflict.  Tracks are numbered by
+ * ascending label, a track's members listed by ascending row.
+ *
+ * Outputs, host arrays sized from N = offsets[n_segs] - offsets[0]:
+ *   track_of[N]                    track of row offsets[0] + i, or -1
+ *   *n_tracks, track_offsets[n_tracks + 1]   (N / 2 + 2 entries provided)
+ *   obs[track_offsets[n_tracks]]   one record per member: its segment, its
+ *                                  index in the segment, and the x, y bit
+ *                                  patterns of its keypoint (N entries provided)
+ *   conflict[n_tracks]             1 where the track is in conflict; all 0
+ *                                  with drop_conflicts (N / 2 + 1 provided)
+ * SIFT_MI_EINVAL, before any device work, for a null argument other than
+ * keep, min_length < 2, a pair naming a segment >= n_segs, decreasing offsets
+ * or pair_offsets, a match index outside its pair's segment, N or the match
+ * count above 2^31 - 1, a d_kps that is not 4-byte aligned.  No pairs, no matches and N == 0 give no tracks.
+ * Only reads d_kps: the device results stay valid; no allocation once the
+ * context's scratch has grown to the call's size. */
+typedef struct {
+    uint32_t min_length;
+    int drop_conflicts;
+} sift_mi_track_params;
+typedef struct {
+    uint32_t seg, idx;
+    float x, y;
+} sift_mi_track_obs;
+int sift_mi_build_tracks_device(sift_mi_ctx* ctx, const sift_mi_keypoint* d_kps, const size_t* offsets,
+                                uint32_t n_segs, const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                const sift_mi_match* matches, const size_t* pair_offsets,
+                                const uint8_t* keep /* may be null */, const sift_mi_track_params* params,
+                                int32_t* track_of, uint32_t* n_tracks, uint32_t* track_offsets,
+                                sift_mi_track_obs* obs, uint8_t* conflict);
+/* Diagnostic: the kernel time of the track calls (two events around the
+ * launch sequence) and the edges (kept matches) they linked; cumulative,
+ * reset by sift_mi_reset_stats. */
+int sift_mi_track_counters(sift_mi_ctx* ctx, double* kernel_ms, uint64_t* edges);
+
 /* ---- the input step before the path ---------------
  * Baseline (SOF0/SOF1) Huffman JPEG, 1 or 3 components -> 8-bit luma, with
  * the arithmetic of the reference's decode: image 0.25.2 `image::open` /
@@ -543,7 +589,9 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        (RANSAC fundamental matrix + inlier refit; sift_mi_fundamental);
  *        sift_mi_match_pairs_guided_device, sift_mi_match_guided,
  *        sift_mi_guided_counters (guided matching under the verified models;
- *        sift_mi_model_kind, sift_mi_guided_params), SIFT_MI_PATH_GUIDED_CULL.
+ *        sift_mi_model_kind, sift_mi_guided_params), SIFT_MI_PATH_GUIDED_CULL;
+ *        sift_mi_build_tracks_device, sift_mi_track_counters (feature tracks
+ *        over the kept matches; sift_mi_track_params, sift_mi_track_obs).
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

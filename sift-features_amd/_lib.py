@@ -26,6 +26,7 @@ EXPORTS = [
     "sift_mi_verify_pairs_device", "sift_mi_verify_matches",
     "sift_mi_verify_pairs_epipolar_device", "sift_mi_verify_matches_epipolar",
     "sift_mi_match_pairs_guided_device", "sift_mi_match_guided", "sift_mi_guided_counters",
+    "sift_mi_build_tracks_device", "sift_mi_track_counters",
     "sift_mi_decode_jpeg", "sift_mi_decode_jpeg_batch", "sift_mi_get_stats",
     "sift_mi_reset_stats",
     "sift_mi_version", "sift_mi_last_error",
@@ -77,6 +78,16 @@ class GuidedParams(ctypes.Structure):
     """include/sift_mi.h sift_mi_guided_params."""
     _fields_ = [("threshold", ctypes.c_float), ("ratio", ctypes.c_float), ("max_distance", ctypes.c_float),
                 ("cross_check", ctypes.c_int)]
+
+
+class TrackParams(ctypes.Structure):
+    """include/sift_mi.h sift_mi_track_params."""
+    _fields_ = [("min_length", ctypes.c_uint32), ("drop_conflicts", ctypes.c_int)]
+
+
+class TrackObs(ctypes.Structure):
+    """include/sift_mi.h sift_mi_track_obs."""
+    _fields_ = [("seg", ctypes.c_uint32), ("idx", ctypes.c_uint32), ("x", ctypes.c_float), ("y", ctypes.c_float)]
 
 
 MODEL_KINDS = {"homography": 0, "fundamental": 1}  # include/sift_mi.h sift_mi_model_kind
@@ -159,6 +170,9 @@ def lib():
         "sift_mi_match_pairs_guided_device": [vp, vp, vp, P(sz), u32, vp, u32, i32, vp, P(GuidedParams), vp, sz, P(sz)],
         "sift_mi_match_guided": [vp, vp, vp, sz, vp, vp, sz, i32, vp, P(GuidedParams), vp, sz, P(sz)],
         "sift_mi_guided_counters": [vp, P(u64), P(u64)],
+        "sift_mi_build_tracks_device": [vp, vp, P(sz), u32, vp, u32, vp, P(sz), vp, P(TrackParams), vp, P(u32), vp,
+                                        vp, vp],
+        "sift_mi_track_counters": [vp, P(f64), P(u64)],
         "sift_mi_jpeg_dims": [vp, sz, P(u32), P(u32)],
         "sift_mi_decode_jpeg": [vp, vp, sz, vp, sz, i32],
         "sift_mi_decode_jpeg_batch": [vp, P(vp), P(sz), u32, vp, sz, sz, i32],

@@ -509,6 +509,133 @@ int verify_run(sift_mi_ctx* c, VerifyKind kind, const OutKp* d_kps, const size_t
     HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
+
+static_assert(sizeof(TrackObs) == sizeof(sift_mi_track_obs), "tracks.hip's record is the C ABI's");
+
+// Tracks over the pairs' kept matches on device keypoints d_kps: checks every
+// segment, pair and match index on the host (no kernel sees an index outside
+// its segment), uploads the matches and the mask, runs launch_tracks on the
+// context stream, reads the two counts back and then exactly the tracks'
+// share of the result arrays.  d_kps is only read.
+int tracks_run(sift_mi_ctx* c, const OutKp* d_kps, const size_t* offsets, uint32_t n_segs,
+               const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
+               const size_t* pair_offsets, const uint8_t* keep, const sift_mi_track_params* prm, int32_t* track_of,
+               uint32_t* n_tracks, uint32_t* track_offsets, sift_mi_track_obs* obs, uint8_t* conflict) {
+    constexpr size_t kMax = 0x7fffffff;
+    if (prm->min_length < 2) return fail(SIFT_MI_EINVAL, "min_length must be >= 2");
+    if (((uintptr_t)d_kps & 3) != 0) return fail(SIFT_MI_EINVAL, "d_kps must be 4-byte aligned");
+    for (uint32_t s = 0; s < n_segs; s++)
+        if (offsets[s + 1] < offsets[s]) return fail(SIFT_MI_EINVAL, "offsets decrease");
+    const size_t row_base = offsets[0], n_rows = offsets[n_segs] - row_base;
+    if (n_rows > kMax) return fail(SIFT_MI_EINVAL, "segments sum to more than 2^31 - 1 rows");
+    for (uint32_t p = 0; p < n_pairs; p++)
+        if (pair_offsets[p + 1] < pair_offsets[p]) return fail(SIFT_MI_EINVAL, "pair_offsets decrease");
+    const size_t m_base = pair_offsets[0], total = pair_offsets[n_pairs] - m_base;
+    if (total > kMax) return fail(SIFT_MI_EINVAL, "more than 2^31 - 1 matches");
+    std::vector<TrackPair> P(n_pairs);
+    for (uint32_t p = 0; p < n_pairs; p++) {
+        const uint32_t qs = pairs[p].query_seg, ts = pairs[p].train_seg;
+        if (qs >= n_segs || ts >= n_segs) return fail(SIFT_MI_EINVAL, "pair names a segment >= n_segs");
+        const size_t nq = offsets[qs + 1] - offsets[qs], nt = offsets[ts + 1] - offsets[ts];
+        for (size_t i = pair_offsets[p]; i < pair_offsets[p + 1]; i++) {
+            const sift_mi_match& mt = matches[i];
+            if (mt.query_idx < 0 || (size_t)mt.query_idx >= nq || mt.train_idx < 0 || (size_t)mt.train_idx >= nt)
+                return fail(SIFT_MI_EINVAL, "match index outside its pair's segment (pair " + std::to_string(p) + ")");
+        }
+        P[p] = TrackPair{(uint32_t)(pair_offsets[p] - m_base), (uint32_t)(offsets[qs] - row_base),
+                         (uint32_t)(offsets[ts] - row_base)};
+    }
+    uint64_t edges = total;
+    if (keep) {
+        edges = 0;
+        for (size_t i = 0; i < total; i++) edges += keep[m_base + i] != 0;
+    }
+    *n_tracks = 0;
+    track_offsets[0] = 0;
+    if (n_rows == 0) return 0;
+
+    CHK(set_device(c));
+    TrackScratch& T = c->tracks;
+    hipStream_t st = c->stream;
+    const size_t cap = n_rows / 2 + 2, n_blocks = (n_rows + 255) / 256;
+    std::vector<uint32_t> seg_rows(n_segs);
+    for (uint32_t s = 0; s < n_segs; s++) seg_rows[s] = (uint32_t)(offsets[s] - row_base);
+    const size_t tmp = track_sort_temp_bytes((uint32_t)n_rows);
+    if (!tmp) return fail(SIFT_MI_EHIP, "radix sort temporary storage query failed");
+    CHK(pool(T.matches, total));
+    if (keep) CHK(pool(T.keep, total));
+    CHK(pool(T.pairs, n_pairs));
+    CHK(pool(T.offs, n_segs));
+    for (DevBuf<uint32_t>* b : {&T.parent, &T.seg_of, &T.label, &T.row, &T.sorted_label, &T.sorted_row, &T.start, &T.end})
+        CHK(pool(*b, n_rows));
+    CHK(pool(T.confl, n_rows));
+    CHK(pool(T.sort_tmp, tmp));
+    CHK(pool(T.bsum, n_blocks));
+    CHK(pool(T.totals, 2));
+    CHK(pool(T.track_offsets, cap));
+    CHK(pool(T.track_of, n_rows));
+    CHK(pool(T.obs, n_rows));
+    CHK(pool(T.conflict, cap));
+    CHK(pool(T.h_totals, 2));
+    if (!T.t0) HIPCHK(hipEventCreate(&T.t0));
+    if (!T.t1) HIPCHK(hipEventCreate(&T.t1));
+
+    HIPCHK(hipMemcpyAsync(T.offs.p, seg_rows.data(), (size_t)n_segs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (total) {  // (with no match the link kernel is not launched and nothing reads these)
+        HIPCHK(hipMemcpyAsync(T.pairs.p, P.data(), (size_t)n_pairs * sizeof(TrackPair), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(T.matches.p, matches + m_base, total * sizeof(VerifyMatch), hipMemcpyHostToDevice, st));
+        if (keep) HIPCHK(hipMemcpyAsync(T.keep.p, keep + m_base, total, hipMemcpyHostToDevice, st));
+    }
+    TrackLaunch L{};
+    L.kps = d_kps + row_base;
+    L.offs = T.offs.p;
+    L.n_segs = n_segs;
+    L.n_rows = (uint32_t)n_rows;
+    L.matches = T.matches.p;
+    L.keep = keep && total ? T.keep.p : nullptr;
+    L.pairs = T.pairs.p;
+    L.n_pairs = n_pairs;
+    L.n_matches = (uint32_t)total;
+    L.min_length = prm->min_length;
+    L.drop_conflicts = prm->drop_conflicts ? 1 : 0;
+    L.parent = T.parent.p;
+    L.seg_of = T.seg_of.p;
+    L.label = T.label.p;
+    L.row = T.row.p;
+    L.sorted_label = T.sorted_label.p;
+    L.sorted_row = T.sorted_row.p;
+    L.start = T.start.p;
+    L.end = T.end.p;
+    L.confl = T.confl.p;
+    L.bsum = T.bsum.p;
+    L.sort_temp = T.sort_tmp.p;
+    L.sort_temp_bytes = tmp;
+    L.totals = T.totals.p;
+    L.track_of = T.track_of.p;
+    L.track_offsets = T.track_offsets.p;
+    L.obs = reinterpret_cast<TrackObs*>(T.obs.p);
+    L.conflict = T.conflict.p;
+    HIPCHK(hipEventRecord(T.t0, st));
+    if (launch_tracks(L, st) != 0) return fail(SIFT_MI_EHIP, "the tracks' radix sort could not be enqueued");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(T.t1, st));
+    // the two counts first: they size the downloads of the other arrays
+    HIPCHK(hipMemcpyAsync(T.h_totals.p, T.totals.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(track_of, T.track_of.p, n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint32_t nt = T.h_totals.p[0], nm = T.h_totals.p[1];
+    if ((size_t)nt + 1 > cap || nm > n_rows) return fail(SIFT_MI_EHIP, "track counts out of range");
+    HIPCHK(hipMemcpyAsync(track_offsets, T.track_offsets.p, ((size_t)nt + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          st));
+    if (nt) HIPCHK(hipMemcpyAsync(conflict, T.conflict.p, nt, hipMemcpyDeviceToHost, st));
+    if (nm) HIPCHK(hipMemcpyAsync(obs, T.obs.p, (size_t)nm * sizeof(TrackObs), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *n_tracks = nt;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, T.t0, T.t1) == hipSuccess) T.kernel_ms += ms;
+    T.edges += edges;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1084,6 +1211,28 @@ int sift_mi_verify_matches_epipolar(sift_mi_ctx* c, const sift_mi_keypoint* quer
                           inliers);
 }
 
+// ---- feature tracks (labelled extension; tracks.hip) ---------------------------
+int sift_mi_build_tracks_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets, uint32_t n_segs,
+                                const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
+                                const size_t* pair_offsets, const uint8_t* keep, const sift_mi_track_params* params,
+                                int32_t* track_of, uint32_t* n_tracks, uint32_t* track_offsets, sift_mi_track_obs* obs,
+                                uint8_t* conflict) {
+    if (!c || !d_kps || !offsets || !pairs || !matches || !pair_offsets || !params || !track_of || !n_tracks ||
+        !track_offsets || !obs || !conflict)
+        return fail(SIFT_MI_EINVAL, "null argument");
+    return match_guard([&]() -> int {
+        return tracks_run(c, reinterpret_cast<const OutKp*>(d_kps), offsets, n_segs, pairs, n_pairs, matches,
+                          pair_offsets, keep, params, track_of, n_tracks, track_offsets, obs, conflict);
+    });
+}
+
+int sift_mi_track_counters(sift_mi_ctx* c, double* kernel_ms, uint64_t* edges) {
+    if (!c || !kernel_ms || !edges) return fail(SIFT_MI_EINVAL, "null argument");
+    *kernel_ms = c->tracks.kernel_ms;
+    *edges = c->tracks.edges;
+    return 0;
+}
+
 int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height) {
     if (!data || !width || !height) return fail(SIFT_MI_EINVAL, "bad arguments");
     return jpeg_guard([&]() -> int {
@@ -1163,6 +1312,8 @@ int sift_mi_reset_stats(sift_mi_ctx* c) {
     if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
     c->stats = sift_mi_stats{};
     c->match.guided_tiles = c->match.guided_culled = 0;
+    c->tracks.kernel_ms = 0;
+    c->tracks.edges = 0;
     if (c->samples.p) {
         CHK(set_device(c));
         CHK(sync_lanes(c));

@@ -310,6 +310,30 @@ struct VerifyScratch {
     DevBuf<uint8_t> mask;
 };
 
+// Pooled scratch of the track builder (sift_mi_build_tracks_device): grows on
+// demand, freed with the context.
+struct TrackScratch {
+    DevBuf<VerifyMatch> matches;
+    DevBuf<uint8_t> keep;
+    DevBuf<TrackPair> pairs;
+    DevBuf<uint32_t> offs;  // per segment its first row
+    DevBuf<uint32_t> parent, seg_of, label, row, sorted_label, sorted_row, start, end;
+    DevBuf<uint8_t> confl, sort_tmp;
+    DevBuf<uint2> bsum;
+    DevBuf<uint32_t> totals, track_offsets;
+    DevBuf<int32_t> track_of;
+    DevBuf<TrackObs> obs;
+    DevBuf<uint8_t> conflict;
+    PinBuf<uint32_t> h_totals;
+    hipEvent_t t0 = nullptr, t1 = nullptr;  // around the kernels
+    double kernel_ms = 0;                   // sift_mi_track_counters
+    uint64_t edges = 0;
+    ~TrackScratch() {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+    }
+};
+
 }  // namespace siftmi
 
 struct sift_mi_ctx {
@@ -382,6 +406,7 @@ struct sift_mi_ctx {
     uint32_t batch_frames = 0;
     siftmi::MatchScratch match;
     siftmi::VerifyScratch verify;
+    siftmi::TrackScratch tracks;
     sift_mi_stats stats{};
 };
 

@@ -382,6 +382,47 @@ void launch_verify_epipolar(const OutKp* kps, const VerifyMatch* matches, const 
                             float4* rec, double* box, float* models, unsigned long long* best, VerifyModel* out,
                             uint8_t* inliers, hipStream_t st);
 
+// tracks.hip
+// Feature tracks: connected components of the kept matches over the arena's
+// rows (LABELLED EXTENSION; tests/tracks_ref.py is the definition).  Rows are
+// relative to the call's first row; pair p's matches are [rec0, next pair's
+// rec0), its segments start at rows qrow0 / trow0.  TrackObs is
+// sift_mi_track_obs.
+struct TrackPair {
+    uint32_t rec0, qrow0, trow0;
+};
+struct TrackObs {
+    uint32_t seg, idx;
+    float x, y;
+};
+constexpr uint32_t kTrackLdsSegs = 2048;  // segment starts k_track_init searches in LDS (more: in global memory)
+struct TrackLaunch {
+    const OutKp* kps;            // the call's first row
+    const uint32_t* offs;        // [n_segs] first row of each segment (offs[0] = 0)
+    uint32_t n_segs, n_rows;
+    const VerifyMatch* matches;  // [n_matches] indices the host has checked against their segments
+    const uint8_t* keep;         // [n_matches] or null: all kept
+    const TrackPair* pairs;      // [n_pairs], rec0 ascending from 0
+    uint32_t n_pairs, n_matches;
+    uint32_t min_length;
+    int drop_conflicts;
+    // scratch, n_rows entries each unless noted
+    uint32_t *parent, *seg_of, *label, *row, *sorted_label, *sorted_row, *start, *end;
+    uint8_t* confl;
+    uint2* bsum;                 // ceil(n_rows / 256)
+    void* sort_temp;
+    size_t sort_temp_bytes;      // track_sort_temp_bytes(n_rows)
+    // results
+    uint32_t* totals;            // tracks, members
+    int32_t* track_of;           // [n_rows]
+    uint32_t* track_offsets;     // [n_rows / 2 + 2]
+    TrackObs* obs;               // [n_rows]
+    uint8_t* conflict;           // [n_rows / 2 + 1]
+};
+size_t track_sort_temp_bytes(uint32_t n_rows);  // 0: the query failed
+// The launch sequence on st (nothing with n_rows == 0); -1 when the sort could not be enqueued.
+int launch_tracks(const TrackLaunch& L, hipStream_t st);
+
 // describe.hip
 // Descriptor work queues: keypoint i belongs to queue i % kDescQueues, which
 // hands out its keypoints in order; 8 counters on separate 128-B lines (one

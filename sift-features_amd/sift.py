@@ -107,6 +107,33 @@ def _f32_image(img):
     return a
 
 
+class Tracks:
+    """Feature tracks (Context.build_tracks_device; LABELLED EXTENSION).
+    `track_of` (N,) int32: the track of each arena row from offsets[0] on, -1
+    for none; `offsets` (len + 1,) uint32 into `obs`, a structured array of
+    (seg, idx, x, y) with one record per member, a track's members by
+    ascending row; `conflict` (len,) bool: the track holds two keypoints of
+    one segment."""
+
+    OBS = np.dtype([("seg", "<u4"), ("idx", "<u4"), ("x", "<f4"), ("y", "<f4")])
+    __slots__ = ("track_of", "offsets", "obs", "conflict")
+
+    def __init__(self, track_of, offsets, obs, conflict):
+        self.track_of, self.offsets, self.obs, self.conflict = track_of, offsets, obs, conflict
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def members(self, t):
+        """The observations of track t."""
+        if not 0 <= t < len(self):
+            raise IndexError(t)
+        return self.obs[self.offsets[t]:self.offsets[t + 1]]
+
+    def __repr__(self):
+        return f"Tracks(n={len(self)}, observations={len(self.obs)})"
+
+
 def _match_arrays(a, lo, hi):
     """Rows lo..hi of a sift_mi_match record array as (query_idx, train_idx, distance)."""
     a = a[lo:hi]
@@ -586,6 +613,76 @@ class Context:
         check(lib().sift_mi_guided_counters(self._h, ctypes.byref(tiles), ctypes.byref(culled)))
         return {"tiles": tiles.value, "culled_waves": culled.value}
 
+    # -- feature tracks (LABELLED EXTENSION: not in the crate) -------------------
+    def build_tracks_device(self, d_kps_ptr, offsets, pairs, matches, keep=None, min_length=2, conflicts="flag"):
+        """LABELLED EXTENSION: link the pairs' matches across the segments
+        into tracks on the device (sift_mi_build_tracks_device; the rule is
+        tests/tracks_ref.py's).  A track is a connected component of the graph
+        whose nodes are the arena rows and whose edges are the kept matches,
+        with at least `min_length` (>= 2) rows.  d_kps_ptr, offsets, pairs,
+        matches as for verify_pairs_device; `keep`: per pair a boolean mask
+        over its matches, or the (model, mask, info) tuple verify_pairs_device
+        returned for it (None: every match).  A track with two keypoints of
+        one segment is in conflict: conflicts="flag" keeps it and marks it in
+        Tracks.conflict, conflicts="drop" leaves it out.  Tracks are numbered
+        by their smallest row.  Returns a Tracks."""
+        if conflicts not in ("flag", "drop"):
+            raise ValueError(f"conflicts must be 'flag' or 'drop', not {conflicts!r}")
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
+            raise ValueError("offsets: n_segs + 1 non-negative row numbers")
+        pr = [(int(a), int(b)) for a, b in pairs]
+        if len(matches) != len(pr):
+            raise ValueError("one (query_idx, train_idx, distance) triple per pair")
+        rec, po = self._match_records(matches)
+        mask = None
+        if keep is not None:
+            if len(keep) != len(pr):
+                raise ValueError("one keep mask per pair")
+            mask = np.zeros(max(int(po[-1]), 1), np.uint8)
+            for p, k in enumerate(keep):
+                k = np.asarray(k[1] if isinstance(k, tuple) else k).astype(bool).reshape(-1)
+                if len(k) != po[p + 1] - po[p]:
+                    raise ValueError(f"keep mask of pair {p}: one entry per match")
+                mask[po[p]:po[p + 1]] = k
+        n = max(int(offs[-1] - offs[0]), 0)
+        c_offs = (ctypes.c_size_t * len(offs))(*[int(v) for v in offs])
+        c_po = (ctypes.c_size_t * len(po))(*[int(v) for v in po])
+        c_pairs = (_lib.SegPair * max(len(pr), 1))(*[_lib.SegPair(a, b) for a, b in pr])
+        track_of = np.empty(max(n, 1), np.int32)
+        t_offs = np.zeros(n // 2 + 2, np.uint32)
+        obs = np.zeros(max(n, 1), Tracks.OBS)
+        conflict = np.zeros(n // 2 + 1, np.uint8)
+        n_tracks = ctypes.c_uint32()
+        prm = _lib.TrackParams(int(min_length), 1 if conflicts == "drop" else 0)
+        check(lib().sift_mi_build_tracks_device(self._h, ctypes.c_void_p(d_kps_ptr), c_offs, len(offs) - 1, c_pairs,
+                                                len(pr), rec.ctypes.data, c_po,
+                                                None if mask is None else mask.ctypes.data, ctypes.byref(prm),
+                                                track_of.ctypes.data, ctypes.byref(n_tracks), t_offs.ctypes.data,
+                                                obs.ctypes.data, conflict.ctypes.data))
+        nt = n_tracks.value
+        t_offs = t_offs[:nt + 1].copy()
+        return Tracks(track_of[:n], t_offs, obs[:int(t_offs[-1])].copy(), conflict[:nt].astype(bool))
+
+    def track_frames(self, offsets, pairs, matches, keep=None, min_length=2, conflicts="flag"):
+        """build_tracks_device on the keypoints the last
+        sift_batch_device(..., fetch=False) left in HBM, e.g. on what
+        match_frames returned as `matches` and verify_frames as `keep`."""
+        if conflicts not in ("flag", "drop"):
+            raise ValueError(f"conflicts must be 'flag' or 'drop', not {conflicts!r}")
+        d_kps, _, n = self.device_results()
+        if int(offsets[-1]) > n:
+            raise ValueError("offsets reach beyond the device results")
+        return self.build_tracks_device(d_kps, offsets, pairs, matches, keep, min_length, conflicts)
+
+    def track_counters(self):
+        """{"kernel_ms", "edges"} of the track calls since the last
+        reset_stats(): the time between two events around their launch
+        sequences and the kept matches they linked (sift_mi_track_counters)."""
+        ms, edges = ctypes.c_double(), ctypes.c_uint64()
+        check(lib().sift_mi_track_counters(self._h, ctypes.byref(ms), ctypes.byref(edges)))
+        return {"kernel_ms": ms.value, "edges": edges.value}
+
     # -- the input step (SURVEY.md 8(f) row 2) ------------------------------
     def decode_jpeg(self, data):
         """Baseline JPEG bytes -> (h, w) u8 luma, as the reference makes its
@@ -826,6 +923,17 @@ def match_guided(desc_q, kps_q, desc_t, kps_t, model_matrix, threshold=3.0, mode
     """LABELLED EXTENSION: Context.match_guided on the default context."""
     return default_context().match_guided(desc_q, kps_q, desc_t, kps_t, model_matrix, threshold, model, ratio,
                                           max_distance, cross_check)
+
+
+def build_tracks_device(d_kps_ptr, offsets, pairs, matches, keep=None, min_length=2, conflicts="flag"):
+    """LABELLED EXTENSION: Context.build_tracks_device on the default context."""
+    return default_context().build_tracks_device(d_kps_ptr, offsets, pairs, matches, keep, min_length, conflicts)
+
+
+def track_frames(offsets, pairs, matches, keep=None, min_length=2, conflicts="flag"):
+    """LABELLED EXTENSION: Context.track_frames on the default context (its
+    last sift_batch_device(..., fetch=False) results)."""
+    return default_context().track_frames(offsets, pairs, matches, keep, min_length, conflicts)
 
 
 def stable_sort_xy_size(keypoints_array):
