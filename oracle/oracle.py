@@ -45,10 +45,14 @@ def lib():
         vp, i32, f32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
         L.oracle_sift.restype = vp
         L.oracle_sift.argtypes = [vp, i32, i32, i32, i32, ctypes.c_int64]
+        L.oracle_sift_f64.restype = vp
+        L.oracle_sift_f64.argtypes = [vp, i32, i32, i32, i32, ctypes.c_int64, i32]
         L.oracle_precompute.restype = vp
         L.oracle_precompute.argtypes = [vp, i32, i32, i32, i32]
         L.oracle_sift_with_precomputed.restype = vp
         L.oracle_sift_with_precomputed.argtypes = [vp, ctypes.c_int64]
+        L.oracle_sift_with_precomputed_f64.restype = vp
+        L.oracle_sift_with_precomputed_f64.argtypes = [vp, ctypes.c_int64, i32]
         L.oracle_pyramid_free.argtypes = [vp]
         L.oracle_pyramid_n_octaves.argtypes = [vp]
         L.oracle_pyramid_dims.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
@@ -64,8 +68,11 @@ def lib():
         L.oracle_result_internal.argtypes = [vp]
         L.oracle_result_descriptors.restype = ctypes.POINTER(ctypes.c_uint8)
         L.oracle_result_descriptors.argtypes = [vp]
+        L.oracle_result_descriptors_f64.restype = ctypes.POINTER(f64)
+        L.oracle_result_descriptors_f64.argtypes = [vp]
         L.oracle_result_free.argtypes = [vp]
         L.oracle_compute_descriptor.argtypes = [vp, i32, i32, f32, f32, f32, f32, vp]
+        L.oracle_compute_descriptor_f64.argtypes = [vp, i32, i32, f32, f32, f32, f32, vp]
         L.oracle_gaussian_blur.argtypes = [vp, i32, i32, f64, i32, vp]
         L.oracle_resize_linear.argtypes = [vp, i32, i32, i32, i32, i32, vp]
         L.oracle_resize_nearest.argtypes = [vp, i32, i32, i32, i32, i32, vp]
@@ -84,13 +91,20 @@ def lib():
 VARIANT_STRICT_EXTREMUM = 256
 VARIANT_HALF_UP_BIN = 512
 VARIANT_F32_ATAN2 = 1024
+# the f32 descriptor's wrong-on-purpose variants (descriptor_body.inc)
+VARIANT_DESC_EXP_CONST = 2048
+VARIANT_DESC_MAG_HALF = 4096
+VARIANT_DESC_ORI_BIAS = 8192
+VARIANT_DESC_LOST_SAMPLE = 16384
+VARIANT_DESC_NO_WRAP = 32768
 
 
 @contextlib.contextmanager
 def set_variant(bits):
     """Run the oracle with arithmetic-variant `bits` (oracle_set_variant in
     sift_oracle.c) inside the `with` block; always back to 0 afterwards.
-    Bits 256, 512 and 1024 are wrong on purpose (test use only)."""
+    Bits 256, 512, 1024 and the VARIANT_DESC_* bits are wrong on purpose (test
+    use only)."""
     lib().oracle_set_variant(int(bits))
     try:
         yield
@@ -111,32 +125,38 @@ def _result(r):
     try:
         n = L.oracle_result_n(r)
         if n == 0:
-            return np.zeros((0, 5), np.float32), np.zeros((0, 128), np.uint8), np.zeros((0, 6), np.int32)
+            return (np.zeros((0, 5), np.float32), np.zeros((0, 128), np.uint8), np.zeros((0, 6), np.int32),
+                    np.zeros((0, 128), np.float64))
         kp = np.ctypeslib.as_array(ctypes.cast(L.oracle_result_keypoints(r), ctypes.POINTER(ctypes.c_float)),
                                    shape=(max(n, 1) * 5,))[: n * 5].reshape(n, 5).copy()
         ext = np.ctypeslib.as_array(ctypes.cast(L.oracle_result_internal(r), ctypes.POINTER(ctypes.c_int32)),
                                     shape=(max(n, 1) * 11,))[: n * 11].reshape(n, 11).copy()
         desc = np.ctypeslib.as_array(L.oracle_result_descriptors(r), shape=(max(n, 1) * 128,))[: n * 128]
         desc = desc.reshape(n, 128).copy()
+        p64 = L.oracle_result_descriptors_f64(r)
+        d64 = np.ctypeslib.as_array(p64, shape=(n * 128,)).reshape(n, 128).copy() if p64 else None
     finally:
         L.oracle_result_free(r)
     # ext columns 5.. are int32: octave, scale, s_init, y_init, x_init, peak
-    return kp, desc, ext[:, 5:].copy()
+    return kp, desc, ext[:, 5:].copy(), d64
 
 
-def sift(img, features_limit=None, profile=PROFILE_OPENCV, internal=False):
+def sift(img, features_limit=None, profile=PROFILE_OPENCV, internal=False, desc_f64=False):
     """Oracle of `sift_with_processing::<P>` (src/lib.rs:76-81).
 
     Returns (keypoints[n,5] f32 (x,y,size,angle,response), descriptors[n,128] u8)
     and, with internal=True, the (octave, scale, s_init, y_init, x_init, peak)
-    table as a third element.
+    table as a third element.  With desc_f64=True a last element is added:
+    the [n,128] float64 array of oracle_compute_descriptor_f64 on the same
+    internal keypoints (flat * norm in double, unrounded, unsaturated).
     """
     img = _u8(img)
     h, w = img.shape
     lim = -1 if features_limit is None else int(features_limit)
-    r = lib().oracle_sift(img.ctypes.data, w, h, w, profile, lim)
-    kp, desc, ext = _result(r)
-    return (kp, desc, ext) if internal else (kp, desc)
+    r = lib().oracle_sift_f64(img.ctypes.data, w, h, w, profile, lim, 1 if desc_f64 else 0)
+    kp, desc, ext, d64 = _result(r)
+    out = (kp, desc, ext) if internal else (kp, desc)
+    return out + (d64,) if desc_f64 else out
 
 
 class Pyramid:
@@ -163,9 +183,12 @@ class Pyramid:
         w, h = self.dims(o)
         return np.ctypeslib.as_array(lib().oracle_pyramid_dog(self._p, o), shape=(5, h, w)).copy()
 
-    def sift_with_precomputed(self, features_limit=None):
+    def sift_with_precomputed(self, features_limit=None, desc_f64=False):
+        """(keypoints, descriptors) and, with desc_f64=True, the f64 descriptor
+        array of `sift(..., desc_f64=True)` as a third element."""
         lim = -1 if features_limit is None else int(features_limit)
-        return _result(lib().oracle_sift_with_precomputed(self._p, lim))[:2]
+        kp, desc, _, d64 = _result(lib().oracle_sift_with_precomputed_f64(self._p, lim, 1 if desc_f64 else 0))
+        return (kp, desc, d64) if desc_f64 else (kp, desc)
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -179,6 +202,17 @@ def compute_descriptor(img, x, y, scale, orientation):
     h, w = img.shape
     out = np.zeros(128, np.uint8)
     lib().oracle_compute_descriptor(img.ctypes.data, w, h, x, y, scale, orientation, out.ctypes.data)
+    return out
+
+
+def compute_descriptor_f64(img, x, y, scale, orientation):
+    """`compute_descriptor` on the same f32 plane and f32 keypoint fields with
+    every operation in double: the 128 values flat * norm, before rounding and
+    the 255 saturation."""
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    h, w = img.shape
+    out = np.zeros(128, np.float64)
+    lib().oracle_compute_descriptor_f64(img.ctypes.data, w, h, x, y, scale, orientation, out.ctypes.data)
     return out
 
 

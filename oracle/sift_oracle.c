@@ -159,7 +159,23 @@ static inline int reflect101(int p, int len) {
  * "Structured patterns"):
  *   256   strict comparisons in is_extremum (> / < for >= / <=)
  *   512   orientation bin by floorf(raw_bin + 0.5f) for roundf (half away)
- *   1024  orientation angle by f32 atan2f for (float)atan2(double) */
+ *   1024  orientation angle by f32 atan2f for (float)atan2(double)
+ * Bits 2048..32768 are WRONG ON PURPOSE, TEST USE ONLY, in the f32 descriptor
+ * (descriptor_body.inc; the f64 instance ignores them): mistakes of a few
+ * hundredths of a byte step, which tests/test_descriptor_ref_cpu.py shows the
+ * f64 rule rejects:
+ *   2048   DESC_EXP_CONST    Gaussian weight exponent constant * (1 + 1e-3)
+ *   4096   DESC_MAG_HALF     mag *= 1.0005f in the lower half window (yi > 0)
+ *   8192   DESC_ORI_BIAS     orientation bin obin + 1e-4f
+ *   16384  DESC_LOST_SAMPLE  the last admitted sample of a window adds nothing
+ *   32768  DESC_NO_WRAP      the o1 contributions dropped when o0 == 7 */
+enum {
+    VARIANT_DESC_EXP_CONST = 2048,
+    VARIANT_DESC_MAG_HALF = 4096,
+    VARIANT_DESC_ORI_BIAS = 8192,
+    VARIANT_DESC_LOST_SAMPLE = 16384,
+    VARIANT_DESC_NO_WRAP = 32768
+};
 static int g_variant = 0;
 void oracle_set_variant(int v) { g_variant = v; }
 
@@ -787,96 +803,48 @@ static void find_keypoints(const opyr_t* p, kpvec_t* out) {
 /* ------------------------------------------------------------------ */
 /* compute_descriptor (src/lib.rs:785-990)                              */
 /* ------------------------------------------------------------------ */
+/* The body lives in descriptor_body.inc, written once over a real type. */
+#define DESC_CORE desc_core_f32
+#define REAL float
+#define DESC_F32 1
+#define R(c) c##f
+#define RF(fn) fn##f
+#include "descriptor_body.inc"
+#undef DESC_CORE
+#undef REAL
+#undef DESC_F32
+#undef R
+#undef RF
+
+#define DESC_CORE desc_core_f64
+#define REAL double
+#define DESC_F32 0
+#define R(c) c
+#define RF(fn) fn
+#include "descriptor_body.inc"
+#undef DESC_CORE
+#undef REAL
+#undef DESC_F32
+#undef R
+#undef RF
+
 void oracle_compute_descriptor(const float* img, int width, int height, float xf, float yf, float scale,
                                float orientation, uint8_t* out) {
-    const int n_hist = DESC_HIST, n_bins = DESC_BINS;
-    const uint64_t x = sat_usize(roundf(xf));
-    const uint64_t y = sat_usize(roundf(yf));
-    const float BIN_ANGLE_STEP = (float)DESC_BINS / 360.0f;
-    const float hist_width = 3.0f * scale;
-    const int radius = sat_i32(roundf(3.0f * scale * sqrtf(2.0f) * (float)(n_hist + 1) * 0.5f));
-    const float rad = orientation * (3.14159265358979323846f / 180.0f);
-    const float sin_ori = sinf(rad), cos_ori = cosf(rad);
-    const float sin_s = sin_ori / hist_width, cos_s = cos_ori / hist_width;
-    float hist[6][6][DESC_BINS];
-    memset(hist, 0, sizeof(hist));
-    for (int yi = -radius; yi <= radius; yi++) {
-        for (int xi = -radius; xi <= radius; xi++) {
-            const float col_rot = (float)xi * cos_s - (float)yi * sin_s;
-            const float row_rot = (float)xi * sin_s + (float)yi * cos_s;
-            float row_bin = row_rot + (float)(n_hist / 2);
-            float col_bin = col_rot + (float)(n_hist / 2);
-            const int32_t ay = (int32_t)y + yi;
-            const int32_t ax = (int32_t)x + xi;
-            if (!(row_bin > -0.5f && row_bin < (float)n_hist + 0.5f && col_bin > -0.5f &&
-                  col_bin < (float)n_hist + 0.5f && ay > 0 && ay < height - 1 && ax > 0 && ax < width - 1))
-                continue;
-            const float* r = img + (size_t)ay * width;
-            const float dx = r[ax + 1] - r[ax - 1];
-            const float dy = img[(size_t)(ay - 1) * width + ax] - img[(size_t)(ay + 1) * width + ax];
-            const float wsq = col_rot * col_rot + row_rot * row_rot;
-            const float weight = expf(wsq * (-2.f / (float)(n_hist * n_hist)));
-            const double deg = atan2((double)dy, (double)dx) * (180.0 / 3.14159265358979323846);
-            const float ori = (float)fmod(deg + 360.0, 360.0) - orientation;
-            float mag = sqrtf(dx * dx + dy * dy);
-            row_bin = row_bin - 0.5f;
-            col_bin = col_bin - 0.5f;
-            mag = mag * weight;
-            const float obin = ori * BIN_ANGLE_STEP;
-            const float row_floor = floorf(row_bin), col_floor = floorf(col_bin), ori_floor = floorf(obin);
-            const float row_frac = row_bin - row_floor, col_frac = col_bin - col_floor, ori_frac = obin - ori_floor;
-            const float c1 = mag * row_frac, c0 = mag - c1;
-            const float c11 = c1 * col_frac, c10 = c1 - c11;
-            const float c01 = c0 * col_frac, c00 = c0 - c01;
-            const float c111 = c11 * ori_frac, c110 = c11 - c111;
-            const float c101 = c10 * ori_frac, c100 = c10 - c101;
-            const float c011 = c01 * ori_frac, c010 = c01 - c011;
-            const float c001 = c00 * ori_frac, c000 = c00 - c001;
-            const uint64_t r1 = sat_usize(row_floor + 1.f), cc1 = sat_usize(col_floor + 1.f);
-            const uint64_t r2 = sat_usize(row_floor + 2.f), cc2 = sat_usize(col_floor + 2.f);
-            float of = ori_floor;
-            if (of < 0.f)
-                of = of + (float)n_bins;
-            else if (of >= (float)n_bins)
-                of = of - (float)n_bins;
-            const uint64_t o0 = sat_usize(of);
-            const uint64_t o1 = o0 + 1 >= (uint64_t)n_bins ? 0 : o0 + 1;
-            hist[r1][cc1][o0] += c000;
-            hist[r1][cc1][o1] += c001;
-            hist[r1][cc2][o0] += c010;
-            hist[r1][cc2][o1] += c011;
-            hist[r2][cc1][o0] += c100;
-            hist[r2][cc1][o1] += c101;
-            hist[r2][cc2][o0] += c110;
-            hist[r2][cc2][o1] += c111;
-        }
-    }
-    float flat[DESC_SIZE];
-    int i = 0;
-    for (int r = 1; r < 5; r++)
-        for (int c = 1; c < 5; c++)
-            for (int o = 0; o < n_bins; o++) flat[i++] = hist[r][c][o];
-    float l2 = 0.0f;
-    for (int ch = 0; ch < DESC_SIZE / 4; ch++) {
-        float s = 0.0f;
-        for (int j = 0; j < 4; j++) s += flat[4 * ch + j] * flat[4 * ch + j];
-        l2 = ch == 0 ? s : l2 + s;
-    }
-    l2 = sqrtf(l2);
-    const float cap = l2 * 0.2f;
-    for (int j = 0; j < DESC_SIZE; j++) flat[j] = fminf(flat[j], cap);
-    float l2c = 0.0f;
-    for (int ch = 0; ch < DESC_SIZE / 4; ch++) {
-        float s = 0.0f;
-        for (int j = 0; j < 4; j++) s += flat[4 * ch + j] * flat[4 * ch + j];
-        l2c = ch == 0 ? s : l2c + s;
-    }
-    l2c = sqrtf(l2c);
-    const float norm = 512.0f / fmaxf(l2c, FLT_EPSILON);
+    float v[DESC_SIZE];
+    desc_core_f32(img, width, height, xf, yf, scale, orientation, v);
     for (int j = 0; j < DESC_SIZE; j++) {
-        const int32_t v = sat_i32(roundf(flat[j] * norm));
-        out[j] = v > 255 ? 255 : (uint8_t)v;
+        const int32_t q = sat_i32(roundf(v[j]));
+        out[j] = q > 255 ? 255 : (uint8_t)q;
     }
+}
+
+/* The f64 reference of the descriptor: the same f32 plane and f32 keypoint
+ * fields, every operation after them in double; out[j] = flat[j] * norm,
+ * unrounded and unsaturated (tests/descriptor_ref.py states the rule that
+ * compares bytes with it). */
+void oracle_compute_descriptor_f64(const float* img, int width, int height, float xf, float yf, float scale,
+                                   float orientation, double* out) {
+    desc_core_f64(img, width, height, xf, yf, scale, orientation, out);
 }
 
 /* ------------------------------------------------------------------ */
@@ -887,6 +855,7 @@ typedef struct {
     okp_t* kps;     /* public KeyPoint (x,y,size x0.5) */
     osk_t* ext;     /* internal SiftKeyPoint + emission key */
     uint8_t* desc;  /* n*128 */
+    double* desc64; /* n*128 of oracle_compute_descriptor_f64, or NULL */
 } ores_t;
 
 static int cmp_resp_desc(const void* a, const void* b) {
@@ -899,7 +868,9 @@ static int cmp_resp_desc(const void* a, const void* b) {
 
 /* features_limit < 0 == None.  With a limit, ties in response keep emission
  * order (the reference's sort_unstable_by leaves tie order unspecified). */
-ores_t* oracle_sift_with_precomputed(const opyr_t* p, int64_t features_limit) {
+/* want_f64: also the f64 descriptor of every internal keypoint
+ * (oracle_result_descriptors_f64). */
+ores_t* oracle_sift_with_precomputed_f64(const opyr_t* p, int64_t features_limit, int want_f64) {
     kpvec_t kv = {0};
     find_keypoints(p, &kv);
     if (features_limit >= 0 && (size_t)features_limit < kv.n) {
@@ -927,6 +898,7 @@ ores_t* oracle_sift_with_precomputed(const opyr_t* p, int64_t features_limit) {
     r->ext = kv.v;
     r->kps = (okp_t*)malloc(sizeof(okp_t) * (kv.n ? kv.n : 1));
     r->desc = (uint8_t*)malloc((size_t)DESC_SIZE * (kv.n ? kv.n : 1));
+    r->desc64 = want_f64 ? (double*)malloc(sizeof(double) * DESC_SIZE * (kv.n ? kv.n : 1)) : NULL;
     /* compute_descriptors (src/lib.rs:759-782) */
     for (size_t i = 0; i < kv.n; i++) {
         const osk_t* kp = &kv.v[i];
@@ -936,6 +908,9 @@ ores_t* oracle_sift_with_precomputed(const opyr_t* p, int64_t features_limit) {
         const float osf = powi_f32(2.0f, -kp->octave);
         const float kp_size = kp->size * osf;
         oracle_compute_descriptor(img, w, h, kp->x * osf, kp->y * osf, kp_size, angle, r->desc + i * DESC_SIZE);
+        if (want_f64)
+            oracle_compute_descriptor_f64(img, w, h, kp->x * osf, kp->y * osf, kp_size, angle,
+                                          r->desc64 + i * DESC_SIZE);
         r->kps[i].x = kp->x * 0.5f;
         r->kps[i].y = kp->y * 0.5f;
         r->kps[i].size = kp->size * 0.5f;
@@ -945,24 +920,34 @@ ores_t* oracle_sift_with_precomputed(const opyr_t* p, int64_t features_limit) {
     return r;
 }
 
+ores_t* oracle_sift_with_precomputed(const opyr_t* p, int64_t features_limit) {
+    return oracle_sift_with_precomputed_f64(p, features_limit, 0);
+}
+
 /* sift_with_processing (src/lib.rs:76-81) */
-ores_t* oracle_sift(const uint8_t* img, int w, int h, int stride, int profile, int64_t features_limit) {
+ores_t* oracle_sift_f64(const uint8_t* img, int w, int h, int stride, int profile, int64_t features_limit,
+                        int want_f64) {
     opyr_t* p = oracle_precompute(img, w, h, stride, profile);
     if (!p) return NULL;
-    ores_t* r = oracle_sift_with_precomputed(p, features_limit);
+    ores_t* r = oracle_sift_with_precomputed_f64(p, features_limit, want_f64);
     oracle_pyramid_free(p);
     return r;
+}
+ores_t* oracle_sift(const uint8_t* img, int w, int h, int stride, int profile, int64_t features_limit) {
+    return oracle_sift_f64(img, w, h, stride, profile, features_limit, 0);
 }
 
 size_t oracle_result_n(const ores_t* r) { return r->n; }
 const okp_t* oracle_result_keypoints(const ores_t* r) { return r->kps; }
 const osk_t* oracle_result_internal(const ores_t* r) { return r->ext; }
 const uint8_t* oracle_result_descriptors(const ores_t* r) { return r->desc; }
+const double* oracle_result_descriptors_f64(const ores_t* r) { return r->desc64; }
 void oracle_result_free(ores_t* r) {
     if (!r) return;
     free(r->kps);
     free(r->ext);
     free(r->desc);
+    free(r->desc64);
     free(r);
 }
 

@@ -357,8 +357,11 @@ __device__ __forceinline__ void describe_wave_exact(const float* __restrict__ im
 // lane-minor layout: conflict-free within a group of NS lanes) with plain read-add-write (LDS float atomics cost ~3 cycles per lane on gfx950,
 // tools/ubench_lds.hip); the 64 slices are then summed per bin.  Per-sample
 // arithmetic is the reference's; only the order of the bin additions differs,
-// so bins agree to f32 rounding and the u8 components to +-1 (the tolerance
-// tests/test_gpu_parity.py states).  describe_wave_exact is the bit-exact
+// so bins agree to f32 rounding: against the f64 evaluation of the same
+// expressions a u8 component differs from the rounded f64 value only where
+// that value is within 7.6e-5 of a .5 boundary (measured on MI355X, the f32
+// oracle itself 1.2e-5; tests/test_gpu_descriptor_f64.py holds the kernel to
+// 4 x that, 3.03e-4 of a byte step).  describe_wave_exact is the bit-exact
 // alternative (sift_mi_set_exact_descriptors).
 //
 // kShare lanes share one slice (64 / kShare slices per wave; lane l: slice
