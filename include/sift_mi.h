@@ -505,6 +505,57 @@ int sift_mi_build_tracks_device(sift_mi_ctx* ctx, const sift_mi_keypoint* d_kps,
  * reset by sift_mi_reset_stats. */
 int sift_mi_track_counters(sift_mi_ctx* ctx, double* kernel_ms, uint64_t* edges);
 
+/* ---- frame-pair proposal (LABELLED EXTENSION: the crate has nothing like it) -
+ * Which frames of an unordered batch to hand to sift_mi_match_pairs_device:
+ * preemptive matching (C. Wu, "Towards linear-time incremental structure from
+ * motion", 2013) of each segment's largest-scale features, on the arena
+ * d_desc / d_kps / offsets[n_segs + 1] that the match and track calls take.
+ * The rule is tests/pairs_ref.py's; every output is integer-exact.
+ *   Subset   S_f = the min(rows of f, subset) rows of segment f with the
+ *            largest keypoint `size`, compared as the u32 pattern of the f32
+ *            (numeric order for the non-negative finite sizes SIFT emits),
+ *            the lower row first among equals; kept in ascending row order.
+ *   Score    scores[a * n_segs + b], a != b = the matches that
+ *            sift_mi_match_ratio(S_a, S_b, ratio, cross_check = 1) keeps
+ *            (ratio == 0: no ratio test; a query without a second neighbour
+ *            fails a ratio test); 0 on the diagonal.  Symmetric when ratio
+ *            == 0, not in general otherwise.
+ *   Proposal s(a, b) = max(scores[a][b], scores[b][a]); a < b is a candidate
+ *            when s >= min_matches.  max_partners == 0: every candidate is
+ *            proposed.  Otherwise each frame keeps its first max_partners
+ *            candidates by (s descending, partner ascending), and a pair is
+ *            proposed when either of its two frames keeps it.
+ * pairs[cap] receives the proposed (a, b), a < b, sorted by (a, b), *n_pairs
+ * their number; scores (n_segs * n_segs, row-major) may be null.  One
+ * workgroup per unordered pair computes both directions; only the scores come
+ * back from the device.
+ * Limits: subset <= 128 by construction (one 128 x 128 tile is a whole frame
+ * pair); frames whose overlap holds few large-scale features score low and
+ * are missed; min_matches is a setting to be chosen for the content, not a
+ * law (DESIGN.md 3.16 has the figures behind the Python default of 8).
+ * SIFT_MI_EINVAL, before any device work, for a null argument other than
+ * scores, subset outside 1..128, a ratio outside [0, 1] or NaN, min_matches
+ * == 0, decreasing offsets, n_segs > 4096 (a 64 MB score matrix), rows
+ * above 2^31 - 1, a d_desc that is not 16-byte or a d_kps that is not 4-byte
+ * aligned; and, after the run, for cap < *n_pairs (then *n_pairs is the
+ * number needed and scores, if given, are written).  n_segs of 0 or 1 gives
+ * no pairs.  Only reads d_desc and d_kps; no allocation once the context's
+ * scratch has grown to the call's size. */
+typedef struct {
+    uint32_t subset;
+    float ratio;
+    uint32_t min_matches;
+    uint32_t max_partners;
+} sift_mi_pair_params;
+int sift_mi_propose_pairs_device(sift_mi_ctx* ctx, const uint8_t* d_desc, const sift_mi_keypoint* d_kps,
+                                 const size_t* offsets, uint32_t n_segs, const sift_mi_pair_params* params,
+                                 uint32_t* scores /* n_segs * n_segs, may be null */, sift_mi_seg_pair* pairs,
+                                 size_t cap, size_t* n_pairs);
+/* Diagnostic: the kernel time of the proposal calls (two events around the
+ * launch sequence) and the frame-pair tiles they computed, n_segs (n_segs -
+ * 1) / 2 a call; cumulative, reset by sift_mi_reset_stats. */
+int sift_mi_pair_counters(sift_mi_ctx* ctx, double* kernel_ms, uint64_t* tiles);
+
 /* ---- the input step before the path ---------------
  * Baseline (SOF0/SOF1) Huffman JPEG, 1 or 3 components -> 8-bit luma, with
  * the arithmetic of the reference's decode: image 0.25.2 `image::open` /
@@ -591,7 +642,9 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        sift_mi_guided_counters (guided matching under the verified models;
  *        sift_mi_model_kind, sift_mi_guided_params), SIFT_MI_PATH_GUIDED_CULL;
  *        sift_mi_build_tracks_device, sift_mi_track_counters (feature tracks
- *        over the kept matches; sift_mi_track_params, sift_mi_track_obs).
+ *        over the kept matches; sift_mi_track_params, sift_mi_track_obs);
+ *        sift_mi_propose_pairs_device, sift_mi_pair_counters (frame pairs
+ *        proposed by preemptive matching; sift_mi_pair_params).
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

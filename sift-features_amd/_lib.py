@@ -27,6 +27,7 @@ EXPORTS = [
     "sift_mi_verify_pairs_epipolar_device", "sift_mi_verify_matches_epipolar",
     "sift_mi_match_pairs_guided_device", "sift_mi_match_guided", "sift_mi_guided_counters",
     "sift_mi_build_tracks_device", "sift_mi_track_counters",
+    "sift_mi_propose_pairs_device", "sift_mi_pair_counters",
     "sift_mi_decode_jpeg", "sift_mi_decode_jpeg_batch", "sift_mi_get_stats",
     "sift_mi_reset_stats",
     "sift_mi_version", "sift_mi_last_error",
@@ -88,6 +89,12 @@ class TrackParams(ctypes.Structure):
 class TrackObs(ctypes.Structure):
     """include/sift_mi.h sift_mi_track_obs."""
     _fields_ = [("seg", ctypes.c_uint32), ("idx", ctypes.c_uint32), ("x", ctypes.c_float), ("y", ctypes.c_float)]
+
+
+class PairParams(ctypes.Structure):
+    """include/sift_mi.h sift_mi_pair_params."""
+    _fields_ = [("subset", ctypes.c_uint32), ("ratio", ctypes.c_float), ("min_matches", ctypes.c_uint32),
+                ("max_partners", ctypes.c_uint32)]
 
 
 MODEL_KINDS = {"homography": 0, "fundamental": 1}  # include/sift_mi.h sift_mi_model_kind
@@ -173,6 +180,8 @@ def lib():
         "sift_mi_build_tracks_device": [vp, vp, P(sz), u32, vp, u32, vp, P(sz), vp, P(TrackParams), vp, P(u32), vp,
                                         vp, vp],
         "sift_mi_track_counters": [vp, P(f64), P(u64)],
+        "sift_mi_propose_pairs_device": [vp, vp, vp, P(sz), u32, P(PairParams), vp, vp, sz, P(sz)],
+        "sift_mi_pair_counters": [vp, P(f64), P(u64)],
         "sift_mi_jpeg_dims": [vp, sz, P(u32), P(u32)],
         "sift_mi_decode_jpeg": [vp, vp, sz, vp, sz, i32],
         "sift_mi_decode_jpeg_batch": [vp, P(vp), P(sz), u32, vp, sz, sz, i32],

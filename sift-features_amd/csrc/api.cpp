@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "host_internal.h"
+#include "pair_propose.h"
 
 using namespace siftmi;
 
@@ -636,6 +637,65 @@ int tracks_run(sift_mi_ctx* c, const OutKp* d_kps, const size_t* offsets, uint32
     T.edges += edges;
     return 0;
 }
+
+constexpr uint32_t kPairMaxSegs = 4096;  // a 64 MB score matrix
+
+// Pair proposal on device rows d_desc and device keypoints d_kps of one
+// arena: every check on the host first, then launch_pairs on the context
+// stream between the two events of sift_mi_pair_counters; only the n_segs^2
+// scores come back, and the proposal runs on them here (pair_propose.h).
+int pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const OutKp* d_kps, const size_t* offsets, uint32_t n_segs,
+              const sift_mi_pair_params* prm, uint32_t* scores, sift_mi_seg_pair* pairs, size_t cap, size_t* n_pairs) {
+    constexpr size_t kMax = 0x7fffffff;
+    if (prm->subset < 1 || prm->subset > kPairSubsetMax) return fail(SIFT_MI_EINVAL, "subset must be 1..128");
+    CHK(check_ratio(prm->ratio));
+    if (prm->min_matches < 1) return fail(SIFT_MI_EINVAL, "min_matches must be >= 1");
+    if (n_segs > kPairMaxSegs) return fail(SIFT_MI_EINVAL, "more than 4096 segments");
+    if (((uintptr_t)d_desc & 15) != 0) return fail(SIFT_MI_EINVAL, "d_desc must be 16-byte aligned");
+    if (((uintptr_t)d_kps & 3) != 0) return fail(SIFT_MI_EINVAL, "d_kps must be 4-byte aligned");
+    for (uint32_t s = 0; s < n_segs; s++)
+        if (offsets[s + 1] < offsets[s]) return fail(SIFT_MI_EINVAL, "offsets decrease");
+    const size_t row_base = offsets[0];
+    if (offsets[n_segs] - row_base > kMax) return fail(SIFT_MI_EINVAL, "segments sum to more than 2^31 - 1 rows");
+    if (n_segs <= 1) {
+        if (n_segs && scores) scores[0] = 0;
+        return 0;
+    }
+    const uint32_t h = prm->subset;
+    const size_t n2 = (size_t)n_segs * n_segs, n_sub = (size_t)n_segs * h;
+    std::vector<uint32_t> seg_rows((size_t)n_segs + 1);
+    for (uint32_t s = 0; s <= n_segs; s++) seg_rows[s] = (uint32_t)(offsets[s] - row_base);
+
+    CHK(set_device(c));
+    PairScratch& S = c->pairs;
+    hipStream_t st = c->stream;
+    CHK(pool(S.offs, (size_t)n_segs + 1));
+    CHK(pool(S.cnt, n_segs));
+    CHK(pool(S.sub_d, n_sub * kDescSize));
+    CHK(pool(S.sub_m, n_sub));
+    CHK(pool(S.score, n2));
+    CHK(pool(S.h_score, n2));
+    if (!S.t0) HIPCHK(hipEventCreate(&S.t0));
+    if (!S.t1) HIPCHK(hipEventCreate(&S.t1));
+    HIPCHK(hipMemcpyAsync(S.offs.p, seg_rows.data(), seg_rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(S.t0, st));
+    launch_pairs(d_kps + row_base, d_desc + row_base * kDescSize, S.offs.p, n_segs, h, prm->ratio, S.cnt.p, S.sub_d.p,
+                 S.sub_m.p, S.score.p, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.t1, st));
+    HIPCHK(hipMemcpyAsync(S.h_score.p, S.score.p, n2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, S.t0, S.t1) == hipSuccess) S.kernel_ms += ms;
+    S.tiles += (uint64_t)n_segs * (n_segs - 1) / 2;
+    if (scores) std::memcpy(scores, S.h_score.p, n2 * sizeof(uint32_t));
+    const std::vector<sift_mi_seg_pair> out =
+        propose_from_scores(S.h_score.p, n_segs, prm->min_matches, prm->max_partners);
+    *n_pairs = out.size();
+    if (cap < out.size()) return fail(SIFT_MI_EINVAL, "cap < number of proposed pairs (*n_pairs)");
+    if (!out.empty()) std::memcpy(pairs, out.data(), out.size() * sizeof(sift_mi_seg_pair));
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1233,6 +1293,26 @@ int sift_mi_track_counters(sift_mi_ctx* c, double* kernel_ms, uint64_t* edges) {
     return 0;
 }
 
+// ---- frame-pair proposal (labelled extension; pairs.hip) -----------------------
+int sift_mi_propose_pairs_device(sift_mi_ctx* c, const uint8_t* d_desc, const sift_mi_keypoint* d_kps,
+                                 const size_t* offsets, uint32_t n_segs, const sift_mi_pair_params* params,
+                                 uint32_t* scores, sift_mi_seg_pair* pairs, size_t cap, size_t* n_pairs) {
+    if (!c || !d_desc || !d_kps || !offsets || !params || !pairs || !n_pairs)
+        return fail(SIFT_MI_EINVAL, "null argument");
+    *n_pairs = 0;
+    return match_guard([&]() -> int {
+        return pairs_run(c, d_desc, reinterpret_cast<const OutKp*>(d_kps), offsets, n_segs, params, scores, pairs, cap,
+                         n_pairs);
+    });
+}
+
+int sift_mi_pair_counters(sift_mi_ctx* c, double* kernel_ms, uint64_t* tiles) {
+    if (!c || !kernel_ms || !tiles) return fail(SIFT_MI_EINVAL, "null argument");
+    *kernel_ms = c->pairs.kernel_ms;
+    *tiles = c->pairs.tiles;
+    return 0;
+}
+
 int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height) {
     if (!data || !width || !height) return fail(SIFT_MI_EINVAL, "bad arguments");
     return jpeg_guard([&]() -> int {
@@ -1314,6 +1394,8 @@ int sift_mi_reset_stats(sift_mi_ctx* c) {
     c->match.guided_tiles = c->match.guided_culled = 0;
     c->tracks.kernel_ms = 0;
     c->tracks.edges = 0;
+    c->pairs.kernel_ms = 0;
+    c->pairs.tiles = 0;
     if (c->samples.p) {
         CHK(set_device(c));
         CHK(sync_lanes(c));

@@ -334,6 +334,24 @@ struct TrackScratch {
     }
 };
 
+// Pooled scratch of the pair proposal (sift_mi_propose_pairs_device): grows on
+// demand, freed with the context.
+struct PairScratch {
+    DevBuf<uint32_t> offs;   // per segment its first row, and the end of the last
+    DevBuf<uint32_t> cnt;    // per segment min(rows, subset)
+    DevBuf<uint8_t> sub_d;   // [n_segs * subset] gathered descriptor rows
+    DevBuf<int> sub_m;       // their |row|^2 - 256 sum(row)
+    DevBuf<uint32_t> score;  // [n_segs * n_segs]
+    PinBuf<uint32_t> h_score;
+    hipEvent_t t0 = nullptr, t1 = nullptr;  // around the kernels
+    double kernel_ms = 0;                   // sift_mi_pair_counters
+    uint64_t tiles = 0;
+    ~PairScratch() {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+    }
+};
+
 }  // namespace siftmi
 
 struct sift_mi_ctx {
@@ -407,6 +425,7 @@ struct sift_mi_ctx {
     siftmi::MatchScratch match;
     siftmi::VerifyScratch verify;
     siftmi::TrackScratch tracks;
+    siftmi::PairScratch pairs;
     sift_mi_stats stats{};
 };
 

@@ -423,6 +423,18 @@ size_t track_sort_temp_bytes(uint32_t n_rows);  // 0: the query failed
 // The launch sequence on st (nothing with n_rows == 0); -1 when the sort could not be enqueued.
 int launch_tracks(const TrackLaunch& L, hipStream_t st);
 
+// pairs.hip
+// Frame-pair proposal by preemptive matching (LABELLED EXTENSION;
+// tests/pairs_ref.py is the definition).  kps / d: the call's first row;
+// offs[n_segs + 1]: the segments' first rows from it.  cnt[n_segs],
+// sub_d[n_segs * h * 128] and sub_m[n_segs * h] are scratch (each segment's
+// min(rows, h) largest-size rows, gathered); score[n_segs * n_segs] receives
+// every entry: score[a][b] = kept matches of S_a -> S_b, 0 on the diagonal.
+// 1 <= h <= kPairSubsetMax; ratio == 0: no ratio test.
+constexpr uint32_t kPairSubsetMax = 128;  // one 128 x 128 tile is a whole frame pair
+void launch_pairs(const OutKp* kps, const uint8_t* d, const uint32_t* offs, uint32_t n_segs, uint32_t h, float ratio,
+                  uint32_t* cnt, uint8_t* sub_d, int* sub_m, uint32_t* score, hipStream_t st);
+
 // describe.hip
 // Descriptor work queues: keypoint i belongs to queue i % kDescQueues, which
 // hands out its keypoints in order; 8 counters on separate 128-B lines (one

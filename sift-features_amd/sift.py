@@ -683,6 +683,54 @@ class Context:
         check(lib().sift_mi_track_counters(self._h, ctypes.byref(ms), ctypes.byref(edges)))
         return {"kernel_ms": ms.value, "edges": edges.value}
 
+    # -- frame-pair proposal (LABELLED EXTENSION: not in the crate) ----------------
+    def propose_pairs_device(self, d_desc_ptr, d_kps_ptr, offsets, subset=128, ratio=0.8, min_matches=8,
+                             max_partners=0):
+        """LABELLED EXTENSION: which segments of an unordered arena to match,
+        by preemptive matching on the device (sift_mi_propose_pairs_device;
+        the rule is tests/pairs_ref.py's).  The `subset` (1..128) rows with
+        the largest keypoint size of every segment are matched between all
+        segment pairs (cross check, ratio test unless ratio is 0 / None);
+        scores[a, b] counts the matches kept from a to b.  A pair a < b with
+        max(scores[a, b], scores[b, a]) >= min_matches is a candidate; with
+        max_partners > 0 each segment keeps its max_partners best candidates
+        and a pair is proposed when either side keeps it.  Returns (pairs,
+        scores): the proposed (a, b) sorted, ready for match_pairs_device, and
+        the (n, n) uint32 score matrix.  The default min_matches suits the
+        synthetic content it was set on, not every input."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
+            raise ValueError("offsets: n_segs + 1 non-negative row numbers")
+        n = len(offs) - 1
+        c_offs = (ctypes.c_size_t * len(offs))(*[int(v) for v in offs])
+        prm = _lib.PairParams(int(subset), float(ratio or 0.0), int(min_matches), int(max_partners))
+        scores = np.zeros((n, n), np.uint32)
+        cap = n * (n - 1) // 2
+        out = (_lib.SegPair * max(cap, 1))()
+        k = ctypes.c_size_t()
+        check(lib().sift_mi_propose_pairs_device(self._h, ctypes.c_void_p(d_desc_ptr), ctypes.c_void_p(d_kps_ptr),
+                                                 c_offs, n, ctypes.byref(prm), scores.ctypes.data if n else None, out,
+                                                 cap, ctypes.byref(k)))
+        return [(out[i].query_seg, out[i].train_seg) for i in range(k.value)], scores
+
+    def propose_frames(self, offsets, subset=128, ratio=0.8, min_matches=8, max_partners=0):
+        """propose_pairs_device on the results the last
+        sift_batch_device(..., fetch=False) left in HBM; the pairs go to
+        match_frames as they are."""
+        d_kps, d_desc, n = self.device_results()
+        if int(offsets[-1]) > n:
+            raise ValueError("offsets reach beyond the device results")
+        return self.propose_pairs_device(d_desc, d_kps, offsets, subset, ratio, min_matches, max_partners)
+
+    def pair_counters(self):
+        """{"kernel_ms", "tiles"} of the proposal calls since the last
+        reset_stats(): the time between two events around their launch
+        sequences and the frame-pair tiles they computed, n (n - 1) / 2 a call
+        (sift_mi_pair_counters)."""
+        ms, tiles = ctypes.c_double(), ctypes.c_uint64()
+        check(lib().sift_mi_pair_counters(self._h, ctypes.byref(ms), ctypes.byref(tiles)))
+        return {"kernel_ms": ms.value, "tiles": tiles.value}
+
     # -- the input step (SURVEY.md 8(f) row 2) ------------------------------
     def decode_jpeg(self, data):
         """Baseline JPEG bytes -> (h, w) u8 luma, as the reference makes its
@@ -934,6 +982,23 @@ def track_frames(offsets, pairs, matches, keep=None, min_length=2, conflicts="fl
     """LABELLED EXTENSION: Context.track_frames on the default context (its
     last sift_batch_device(..., fetch=False) results)."""
     return default_context().track_frames(offsets, pairs, matches, keep, min_length, conflicts)
+
+
+def propose_pairs_device(d_desc_ptr, d_kps_ptr, offsets, subset=128, ratio=0.8, min_matches=8, max_partners=0):
+    """LABELLED EXTENSION: Context.propose_pairs_device on the default context."""
+    return default_context().propose_pairs_device(d_desc_ptr, d_kps_ptr, offsets, subset, ratio, min_matches,
+                                                  max_partners)
+
+
+def propose_frames(offsets, subset=128, ratio=0.8, min_matches=8, max_partners=0):
+    """LABELLED EXTENSION: Context.propose_frames on the default context (its
+    last sift_batch_device(..., fetch=False) results)."""
+    return default_context().propose_frames(offsets, subset, ratio, min_matches, max_partners)
+
+
+def pair_counters():
+    """LABELLED EXTENSION: Context.pair_counters on the default context."""
+    return default_context().pair_counters()
 
 
 def stable_sort_xy_size(keypoints_array):
