@@ -62,8 +62,28 @@ typedef struct sift_mi_ctx sift_mi_ctx;
 int sift_mi_create(int device_ordinal, sift_mi_profile profile, sift_mi_ctx** out);
 void sift_mi_destroy(sift_mi_ctx* ctx);
 
-/* Run subsequent work on an external hipStream_t (e.g. torch's current
- * stream); NULL restores the context-owned stream. */
+/* Run subsequent work on an external hipStream_t (e.g. a torch side stream);
+ * NULL restores the context-owned stream.
+ *   Order: every kernel and copy of a later call -- also those the library
+ *   runs on streams of its own (pipeline lane 1, the octave and descriptor
+ *   streams, the result copies) -- is ordered after the work already enqueued
+ *   on that stream when the call is made.  Frames, descriptors or keypoints
+ *   produced by a kernel on the stream can be handed over without a host
+ *   synchronisation, and an output buffer (sift_mi_decode_jpeg,
+ *   sift_mi_decode_jpeg_batch) is written after earlier writes to it there.
+ *   Completion: every entry point, without exception, returns after its
+ *   results are complete.  That includes results left in device memory
+ *   (sift_mi_device_results after a keep_on_device call, the frames the JPEG
+ *   decode calls write): work enqueued on any stream after the call returns
+ *   may read them.
+ *   Lifetime: the stream must outlive the context, or be reset to NULL before
+ *   it is destroyed (sift_mi_destroy synchronises the stream in force).
+ *   NULL is the context's own stream, created hipStreamNonBlocking: it does
+ *   not synchronise with the legacy default stream (handle 0).  A caller whose
+ *   work runs on the legacy default stream must synchronise before the call,
+ *   or use a side stream and pass that.
+ *   With SIFT_MI_PATH_GRAPH the stream is part of the graph's key: after a
+ *   change of stream the next identical call is captured anew. */
 int sift_mi_set_stream(sift_mi_ctx* ctx, void* hip_stream);
 
 /* Images per internal pipeline chunk for batch calls (0 = automatic). */

@@ -930,14 +930,30 @@ int enqueue_single_graph(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_p
         if (c->graph) (void)hipGraphDestroy(c->graph);
         c->gexec = nullptr;
         c->graph = nullptr;
+        const sift_mi_stats stats0 = c->stats;
         HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
         const int rc = enqueue_chunk(c, 0, d_frames, frame_pitch, stride, m, limit, 0, true);
         hipGraph_t g = nullptr;
         const hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc || e != hipSuccess || !g || g_alloc_gen.load() != k.gen) {
+        if (rc || e != hipSuccess || !g) {
             if (g) (void)hipGraphDestroy(g);
             c->gseen_ok = false;
             return rc ? rc : fail(SIFT_MI_EHIP, std::string("graph capture failed: ") + hipGetErrorString(e));
+        }
+        if (g_alloc_gen.load() != k.gen) {
+            // something was (re)allocated during the capture.  The counter is
+            // process-wide, so this is another context on another thread, or
+            // this context itself (a buffer grown inside enqueue_chunk); in
+            // neither case an error.  The capture ran nothing, so drop the
+            // graph and let the caller enqueue the chunk plainly: that run
+            // uses the buffers as they now are.  The next identical call
+            // starts over as a first sighting.  (A neighbour that allocates
+            // steadily keeps moving the key, so no graph is captured beside
+            // it: slower, not wrong.)
+            (void)hipGraphDestroy(g);
+            c->gseen_ok = false;
+            c->stats = stats0;  // (the plain run counts its launches itself)
+            return 0;
         }
         if (hipGraphInstantiate(&c->gexec, g, nullptr, nullptr, 0) != hipSuccess) {
             (void)hipGraphDestroy(g);

@@ -176,6 +176,21 @@ class Context:
 
     # -- configuration ----------------------------------------------------
     def set_stream(self, hip_stream_handle):
+        """Run later calls on the caller's hipStream_t (sift_mi_set_stream),
+        e.g. `torch.cuda.Stream().cuda_stream`: every kernel and copy of a
+        call is ordered after the work already enqueued on that stream, so
+        inputs produced there need no host synchronisation, and every call
+        returns after its results are complete.  Close the context, or
+        set_stream(None), before the stream is destroyed.
+
+        None or 0 restores the context's own non-blocking stream, which does
+        NOT synchronise with the legacy default stream.  torch's default
+        stream is that stream: `torch.cuda.current_stream().cuda_stream` is 0
+        there (observed on the MI355X with torch 2.10 / ROCm 7.0), so passing
+        it selects the context's own stream and orders nothing.  A caller on
+        torch's default stream must synchronise before the call
+        (`torch.cuda.current_stream().synchronize()`), or do its work on a
+        side stream and pass that."""
         check(lib().sift_mi_set_stream(self._h, ctypes.c_void_p(hip_stream_handle or 0)))
 
     def set_exact_descriptors(self, exact=True):
