@@ -18,7 +18,7 @@
 static void DESC_CORE(const float* img, int width, int height, float xf, float yf, float scale_in,
                       float orientation_in, REAL* out) {
     const int n_hist = DESC_HIST, n_bins = DESC_BINS;
-    const int variant = DESC_F32 ? g_variant : 0;
+    const int variant = DESC_F32 ? (int)(g_variant & 0xffff) : 0;
     const uint64_t x = sat_usize(roundf(xf));
     const uint64_t y = sat_usize(roundf(yf));
     const REAL scale = (REAL)scale_in, orientation = (REAL)orientation_in;

@@ -82,7 +82,7 @@ def lib():
         L.oracle_octave_sigmas.argtypes = [vp]
         L.oracle_seed_sigma.restype = f64
         L.oracle_match.argtypes = [vp, i32, vp, i32, i32, vp, vp]
-        L.oracle_set_variant.argtypes = [i32]
+        L.oracle_set_variant.argtypes = [ctypes.c_int64]
         L.oracle_set_variant.restype = None
         _lib = L
     return _lib
@@ -97,14 +97,32 @@ VARIANT_DESC_MAG_HALF = 4096
 VARIANT_DESC_ORI_BIAS = 8192
 VARIANT_DESC_LOST_SAMPLE = 16384
 VARIANT_DESC_NO_WRAP = 32768
+# the wrong-on-purpose variants of interpolate() and of the orientation patch
+# and peak rules (sift_oracle.c, bits 16..31 of the 64-bit switch)
+VARIANT_STEPS4 = 1 << 16
+VARIANT_STEPS6 = 1 << 17
+VARIANT_MOVE_TRUNC = 1 << 18
+VARIANT_MOVE_RINT = 1 << 19
+VARIANT_BORDER_HI_X = 1 << 20
+VARIANT_BORDER_HI_Y = 1 << 21
+VARIANT_BORDER_LO_X = 1 << 22
+VARIANT_BORDER_LO_Y = 1 << 23
+VARIANT_SCALE_HI = 1 << 24
+VARIANT_SCALE_LO = 1 << 25
+VARIANT_NO_NEG_WRAP = 1 << 26
+VARIANT_RADIUS_TRUNC = 1 << 27
+VARIANT_ROWS_HI = 1 << 28
+VARIANT_ROWS_LO = 1 << 29
+VARIANT_COLS_HI = 1 << 30
+VARIANT_COLS_LO = 1 << 31
 
 
 @contextlib.contextmanager
 def set_variant(bits):
     """Run the oracle with arithmetic-variant `bits` (oracle_set_variant in
     sift_oracle.c) inside the `with` block; always back to 0 afterwards.
-    Bits 256, 512, 1024 and the VARIANT_DESC_* bits are wrong on purpose (test
-    use only)."""
+    Bits 256, 512, 1024, the VARIANT_DESC_* bits and bits 16..31 are wrong on
+    purpose (test use only)."""
     lib().oracle_set_variant(int(bits))
     try:
         yield
@@ -183,12 +201,14 @@ class Pyramid:
         w, h = self.dims(o)
         return np.ctypeslib.as_array(lib().oracle_pyramid_dog(self._p, o), shape=(5, h, w)).copy()
 
-    def sift_with_precomputed(self, features_limit=None, desc_f64=False):
-        """(keypoints, descriptors) and, with desc_f64=True, the f64 descriptor
-        array of `sift(..., desc_f64=True)` as a third element."""
+    def sift_with_precomputed(self, features_limit=None, desc_f64=False, internal=False):
+        """(keypoints, descriptors); with internal=True the internal table of
+        `sift(..., internal=True)` is added, and with desc_f64=True, last, the
+        f64 descriptor array of `sift(..., desc_f64=True)`."""
         lim = -1 if features_limit is None else int(features_limit)
-        kp, desc, _, d64 = _result(lib().oracle_sift_with_precomputed_f64(self._p, lim, 1 if desc_f64 else 0))
-        return (kp, desc, d64) if desc_f64 else (kp, desc)
+        kp, desc, ext, d64 = _result(lib().oracle_sift_with_precomputed_f64(self._p, lim, 1 if desc_f64 else 0))
+        out = (kp, desc, ext) if internal else (kp, desc)
+        return out + (d64,) if desc_f64 else out
 
     def __del__(self):
         if getattr(self, "_p", None):

@@ -168,7 +168,30 @@ static inline int reflect101(int p, int len) {
  *   4096   DESC_MAG_HALF     mag *= 1.0005f in the lower half window (yi > 0)
  *   8192   DESC_ORI_BIAS     orientation bin obin + 1e-4f
  *   16384  DESC_LOST_SAMPLE  the last admitted sample of a window adds nothing
- *   32768  DESC_NO_WRAP      the o1 contributions dropped when o0 == 7 */
+ *   32768  DESC_NO_WRAP      the o1 contributions dropped when o0 == 7
+ * Bits 16..31 (the switch is 64 bits wide) are WRONG ON PURPOSE, TEST USE
+ * ONLY, in the decisions between the extremum test and the descriptor:
+ * interpolate() and the orientation patch and peak rules.  Each one only moves
+ * a bound by one, changes one rounding or one count, and none can read outside
+ * the planes: a position accepted by a moved border bound is still 4 pixels
+ * inside (the neighbourhood reaches 1), the other bounds only tighten.
+ * tests/test_refine_variants_cpu.py shows which registered patterns notice:
+ *   1<<16  STEPS4        4 Newton steps for 5
+ *   1<<17  STEPS6        6 Newton steps for 5
+ *   1<<18  MOVE_TRUNC    the move by truncf(offset) for roundf
+ *   1<<19  MOVE_RINT     the move by rintf(offset) (half to even) for roundf
+ *   1<<20  BORDER_HI_X   a move may end on column w - 5 (nx >= w - 5 + 1)
+ *   1<<21  BORDER_HI_Y   a move may end on row h - 5
+ *   1<<22  BORDER_LO_X   a move may end on column 4 (nx < 5 - 1)
+ *   1<<23  BORDER_LO_Y   a move may end on row 4
+ *   1<<24  SCALE_HI      a move must end on a scale <= SCALES_PER_OCTAVE - 1
+ *   1<<25  SCALE_LO      a move must end on a scale >= 2
+ *   1<<26  NO_NEG_WRAP   a negative interpolated orientation bin is not wrapped
+ *   1<<27  RADIUS_TRUNC  orientation patch radius by truncation for roundf
+ *   1<<28  ROWS_HI       orientation patch: last admitted row dropped (yy >= h - 2)
+ *   1<<29  ROWS_LO       orientation patch: first admitted row dropped (yy <= 1)
+ *   1<<30  COLS_HI       the same on the columns (xx >= w - 2)
+ *   1<<31  COLS_LO       the same on the columns (xx <= 1) */
 enum {
     VARIANT_DESC_EXP_CONST = 2048,
     VARIANT_DESC_MAG_HALF = 4096,
@@ -176,8 +199,24 @@ enum {
     VARIANT_DESC_LOST_SAMPLE = 16384,
     VARIANT_DESC_NO_WRAP = 32768
 };
-static int g_variant = 0;
-void oracle_set_variant(int v) { g_variant = v; }
+#define VARIANT_STEPS4 ((int64_t)1 << 16)
+#define VARIANT_STEPS6 ((int64_t)1 << 17)
+#define VARIANT_MOVE_TRUNC ((int64_t)1 << 18)
+#define VARIANT_MOVE_RINT ((int64_t)1 << 19)
+#define VARIANT_BORDER_HI_X ((int64_t)1 << 20)
+#define VARIANT_BORDER_HI_Y ((int64_t)1 << 21)
+#define VARIANT_BORDER_LO_X ((int64_t)1 << 22)
+#define VARIANT_BORDER_LO_Y ((int64_t)1 << 23)
+#define VARIANT_SCALE_HI ((int64_t)1 << 24)
+#define VARIANT_SCALE_LO ((int64_t)1 << 25)
+#define VARIANT_NO_NEG_WRAP ((int64_t)1 << 26)
+#define VARIANT_RADIUS_TRUNC ((int64_t)1 << 27)
+#define VARIANT_ROWS_HI ((int64_t)1 << 28)
+#define VARIANT_ROWS_LO ((int64_t)1 << 29)
+#define VARIANT_COLS_HI ((int64_t)1 << 30)
+#define VARIANT_COLS_LO ((int64_t)1 << 31)
+static int64_t g_variant = 0;
+void oracle_set_variant(int64_t v) { g_variant = v; }
 
 /* Separable filter: RowFilter<float,float,RowVec_32f> (fma chain from the
  * leftmost tap), then SymmColumnFilter<SymmColumnVec_32f> (centre product,
@@ -605,7 +644,8 @@ typedef struct {
 /* interpolate_extremum (src/lib.rs:525-603) */
 static int interpolate(const float* dog, int w, int h, int scale, int x, int y, interp_t* out) {
     const size_t P = (size_t)w * h;
-    for (int it = 0; it < 5; it++) {
+    const int steps = (g_variant & VARIANT_STEPS4) ? 4 : (g_variant & VARIANT_STEPS6) ? 6 : 5;
+    for (int it = 0; it < steps; it++) {
         const float* prev = dog + (size_t)(scale - 1) * P;
         const float* curr = dog + (size_t)scale * P;
         const float* next = dog + (size_t)(scale + 1) * P;
@@ -644,12 +684,21 @@ static int interpolate(const float* dog, int w, int h, int scale, int x, int y, 
         }
         /* saturating `as isize`; clamp so the int64 sum cannot overflow */
         int64_t rx = sat_i64(roundf(ox)), ry = sat_i64(roundf(oy)), rs = sat_i64(roundf(os));
+        if (g_variant & VARIANT_MOVE_TRUNC) /* wrong on purpose */
+            rx = sat_i64(truncf(ox)), ry = sat_i64(truncf(oy)), rs = sat_i64(truncf(os));
+        if (g_variant & VARIANT_MOVE_RINT) /* wrong on purpose (round-to-nearest-even mode) */
+            rx = sat_i64(rintf(ox)), ry = sat_i64(rintf(oy)), rs = sat_i64(rintf(os));
         const int64_t LIM = (int64_t)1 << 40;
         if (rx > LIM || rx < -LIM || ry > LIM || ry < -LIM || rs > LIM || rs < -LIM) return 0;
         const int64_t nx = x + rx, ny = y + ry, ns = scale + rs;
-        if (!(ns >= 1 && ns <= SCALES_PER_OCTAVE) || nx < IMAGE_BORDER || nx >= w - IMAGE_BORDER || ny < IMAGE_BORDER ||
-            ny >= h - IMAGE_BORDER)
-            return 0;
+        /* the bounds; each wrong-on-purpose variant moves one of them by one */
+        const int64_t s_lo = (g_variant & VARIANT_SCALE_LO) ? 2 : 1;
+        const int64_t s_hi = (g_variant & VARIANT_SCALE_HI) ? SCALES_PER_OCTAVE - 1 : SCALES_PER_OCTAVE;
+        const int64_t x_lo = (g_variant & VARIANT_BORDER_LO_X) ? IMAGE_BORDER - 1 : IMAGE_BORDER;
+        const int64_t y_lo = (g_variant & VARIANT_BORDER_LO_Y) ? IMAGE_BORDER - 1 : IMAGE_BORDER;
+        const int64_t x_hi = (g_variant & VARIANT_BORDER_HI_X) ? w - IMAGE_BORDER + 1 : w - IMAGE_BORDER;
+        const int64_t y_hi = (g_variant & VARIANT_BORDER_HI_Y) ? h - IMAGE_BORDER + 1 : h - IMAGE_BORDER;
+        if (!(ns >= s_lo && ns <= s_hi) || nx < x_lo || nx >= x_hi || ny < y_lo || ny >= y_hi) return 0;
         x = (int)nx;
         y = (int)ny;
         scale = (int)ns;
@@ -691,14 +740,17 @@ void oracle_orientation_hist(const float* img, int w, int h, int x, int y, int r
     const float bin_step = (float)n_bins / (3.14159265358979323846f * 2.f);
     float raw[ORI_BINS + 4];
     for (int i = 0; i < n_bins + 4; i++) raw[i] = 0.0f;
+    /* the admitted rows and columns; each wrong-on-purpose variant drops one */
+    const int64_t y_min = (g_variant & VARIANT_ROWS_LO) ? 1 : 0, y_max = (g_variant & VARIANT_ROWS_HI) ? h - 2 : h - 1;
+    const int64_t x_min = (g_variant & VARIANT_COLS_LO) ? 1 : 0, x_max = (g_variant & VARIANT_COLS_HI) ? w - 2 : w - 1;
     for (int yp = -radius; yp <= radius; yp++) {
         if (yp <= -y) continue;
         const int64_t yy = (int64_t)y + yp;
-        if (yy <= 0 || yy >= h - 1) continue;
+        if (yy <= y_min || yy >= y_max) continue;
         for (int xp = -radius; xp <= radius; xp++) {
             if (xp <= -x) continue;
             const int64_t xx = (int64_t)x + xp;
-            if (xx <= 0 || xx >= w - 1) continue;
+            if (xx <= x_min || xx >= x_max) continue;
             const float* r = img + (size_t)yy * w;
             const float dx = r[xx + 1] - r[xx - 1];
             const float dy = img[(size_t)(yy - 1) * w + xx] - img[(size_t)(yy + 1) * w + xx];
@@ -761,7 +813,9 @@ static void find_keypoints(const opyr_t* p, kpvec_t* out) {
                         (float)0.8 * ((g_variant & 128) ? exp2f(((float)pt.scale + pt.off_s) / (float)SCALES_PER_OCTAVE) : powf(2.0f, ((float)pt.scale + pt.off_s) / (float)SCALES_PER_OCTAVE)) * 2.f;
                     const float kp_x = ((float)pt.x + pt.off_x) * osf;
                     const float kp_y = ((float)pt.y + pt.off_y) * osf;
-                    const int radius = sat_i32(roundf(3.f * 1.5f * kp_scale));
+                    const int radius = (g_variant & VARIANT_RADIUS_TRUNC) /* wrong on purpose */
+                                           ? sat_i32(truncf(3.f * 1.5f * kp_scale))
+                                           : sat_i32(roundf(3.f * 1.5f * kp_scale));
                     float hist[ORI_BINS];
                     oracle_orientation_hist(p->gauss[o] + (size_t)pt.scale * P, w, h, pt.x, pt.y, radius,
                                             1.5f * kp_scale, hist);
@@ -775,7 +829,7 @@ static void find_keypoints(const opyr_t* p, kpvec_t* out) {
                         if (hist[k] > hist[km] && hist[k] > hist[kq] && hist[k] >= thr) {
                             const float interp = (hist[km] - hist[kq]) / (hist[km] - 2.0f * hist[k] + hist[kq]);
                             float bin = (float)k + 0.5f * interp;
-                            if (bin < 0.0f)
+                            if (bin < 0.0f && !(g_variant & VARIANT_NO_NEG_WRAP))
                                 bin = (float)ORI_BINS + bin;
                             else if (bin >= (float)ORI_BINS)
                                 bin = bin - (float)ORI_BINS;

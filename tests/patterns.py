@@ -103,6 +103,104 @@ def edge_dots(h, w):
     return a
 
 
+def box_noise(h, w, seed, k, gain):
+    """u8 noise under a k x k box filter, its contrast stretched by `gain`
+    about mid-grey: integer arithmetic throughout."""
+    n = np.random.default_rng(seed).integers(0, 256, (h + k - 1, w + k - 1), dtype=np.uint8).astype(np.int64)
+    c = np.zeros((h + k, w + k), np.int64)
+    c[1:, 1:] = n.cumsum(0).cumsum(1)
+    s = c[k:, k:] - c[:-k, k:] - c[k:, :-k] + c[:-k, :-k]
+    return np.clip(128 + ((2 * s - 255 * k * k) * gain) // (2 * k * k), 0, 255).astype(np.uint8)
+
+
+def kron_noise(h, w, seed, b):
+    """u8 noise in b x b blocks."""
+    c = np.random.default_rng(seed).integers(0, 256, (h // b + 1, w // b + 1), dtype=np.uint8)
+    return np.kron(c, np.ones((b, b), np.uint8))[:h, :w].astype(np.uint8)
+
+
+def streaks(h, w, seed):
+    """Elongated quartic bumps (aspect 2-3.5, slope between 1/2 and 2 either
+    way) on mid-grey: one about every 8 px along each border, 0.5-5 px inside
+    it, and 40 in the interior.  Elongated extrema are the ill-conditioned
+    ones: a cross term of the Hessian can carry the Newton offset of one
+    coordinate past 0.5 although the pixel is the discrete extremum.  Only
+    + - * / and floor: no libm call decides a pixel."""
+    rng = np.random.default_rng(seed)
+    y, x = _grid(h, w)
+    a = np.full((h, w), 128.0)
+    cs = []
+    for side in range(4):
+        length = w if side < 2 else h
+        n = length // 8
+        t = (np.arange(n) + 0.5) * 8 + rng.uniform(-3, 3, n)
+        d = rng.uniform(0.5, 5.0, n)
+        for ti, di in zip(t, d):
+            cs.append([(di, ti), (h - 1 - di, ti), (ti, di), (ti, w - 1 - di)][side])
+    for _ in range(40):
+        cs.append((rng.uniform(8, h - 8), rng.uniform(8, w - 8)))
+    for cy, cx in cs:
+        b = rng.uniform(1.2, 3.0)
+        asp = rng.uniform(2.0, 3.5)
+        m = rng.choice([-1.0, 1.0]) * rng.uniform(0.5, 2.0)
+        nrm2 = 1.0 + m * m
+        amp = rng.choice([-1.0, 1.0]) * rng.uniform(50, 127)
+        u = (x - cx) + m * (y - cy)
+        v = m * (x - cx) - (y - cy)
+        q = np.maximum(0.0, 1.0 - (u * u / (asp * asp * b * b) + v * v / (b * b)) / nrm2)
+        a += amp * q * q
+    return np.clip(np.floor(a + 0.5), 0, 255).astype(np.uint8)
+
+
+# the kinds of frame a mosaic cell is cut from
+MOSAIC_SOURCES = [("box", 3, 2), ("box", 5, 3), ("box", 7, 4), ("kron", 2), ("kron", 3), ("kron", 4), ("streaks",)]
+MOSAIC_CELL = 32
+
+
+def mosaic(h, w, cells):
+    """cells[i][j] = (kind, seed): the 32 x 32 cell (i, j) is cut, in place,
+    from the h x w frame of MOSAIC_SOURCES[kind] with that seed; the last
+    row and column of cells take the remainder of the frame.
+    Every cell is a window of a WHOLE source frame: its pixels depend on that
+    frame's full random stream, so generating only the window would give
+    another image (test_patterns_cpu.COUNTS would notice).  A dozen whole
+    frames per mosaic is affordable because make() builds each pattern once."""
+    a = np.zeros((h, w), np.uint8)
+    ny, nx = len(cells), len(cells[0])
+    for i in range(ny):
+        for j in range(nx):
+            kind, seed = cells[i][j]
+            src = MOSAIC_SOURCES[kind]
+            full = (box_noise(h, w, seed, src[1], src[2]) if src[0] == "box"
+                    else kron_noise(h, w, seed, src[1]) if src[0] == "kron" else streaks(h, w, seed))
+            y0, y1 = i * MOSAIC_CELL, (h if i == ny - 1 else (i + 1) * MOSAIC_CELL)
+            x0, x1 = j * MOSAIC_CELL, (w if j == nx - 1 else (j + 1) * MOSAIC_CELL)
+            a[y0:y1, x0:x1] = full[y0:y1, x0:x1]
+    return a
+
+
+# The refinement fixtures (tests/test_refine_variants_cpu.py).  The decisions
+# of interpolate_extremum that they exist for are rare: a Newton move that ends
+# exactly one column or row past a border, a refinement that converges on its
+# fifth evaluation or gives up after it.  A white-noise or blob frame has a
+# fraction of one such keypoint, so the cells below were FOUND, not designed:
+# a CPU search (coordinate ascent: for one cell at a time, draw 24-40 random
+# (kind, seed) pairs, run the oracle and its wrong-on-purpose variants on the
+# whole mosaic in both profiles, keep the pair that raises the number of
+# extremum records the variants change; a few sweeps over the cells).  The
+# generators need only these constants.
+BORDER_MOSAIC_CELLS = [
+    [(2, 1771), (5, 428), (3, 1101), (4, 5400), (5, 6219)],
+    [(5, 3893), (3, 464), (3, 7090), (4, 34), (5, 7815)],
+    [(3, 2100), (4, 8959), (4, 2050), (5, 2371), (5, 4896)],
+]
+DRIFT_MOSAIC_CELLS = [
+    [(5, 1524), (4, 7672), (4, 8031), (4, 7550)],
+    [(2, 1888), (2, 2839), (0, 5199), (6, 5349)],
+    [(4, 1298), (6, 34), (5, 7297), (5, 4765)],
+]
+
+
 # name -> (H, W, generator(h, w))
 REGISTRY = {
     "checker5": (96, 128, lambda h, w: checker(h, w, 5)),
@@ -129,6 +227,14 @@ REGISTRY = {
     "white_96x128": (96, 128, lambda h, w: flat(h, w, 255)),
     "step_96x128": (96, 128, step),
     "flat77_96x128": (96, 128, lambda h, w: flat(h, w, 77)),
+    # the refinement fixtures: Newton moves onto the four border lines, and
+    # refinements that take all five evaluations
+    "border_mosaic": (97, 161, lambda h, w: mosaic(h, w, BORDER_MOSAIC_CELLS)),
+    "drift_mosaic": (96, 128, lambda h, w: mosaic(h, w, DRIFT_MOSAIC_CELLS)),
+    # seed 13 of 80 streak frames tried: in the OpenCV profile three
+    # refinements converge on a sixth evaluation (which the reference never
+    # makes) and three moves have a half-integer offset (roundf against rintf)
+    "streaks13": (96, 128, lambda h, w: streaks(h, w, 13)),
 }
 
 # the patterns that yield no keypoint in either profile

@@ -107,6 +107,7 @@ COUNTS = {
     "rings": (15, 13), "blocks4": (394, 348), "blocks6": (309, 738), "bigsq": (2, 4), "edge_dots": (4, 8),
     "white": (0, 0), "step": (0, 0), "stars_inv": (0, 0), "diag7": (1, 0),
     "white_96x128": (0, 0), "step_96x128": (0, 0), "flat77_96x128": (0, 0),
+    "border_mosaic": (455, 429), "drift_mosaic": (338, 346), "streaks13": (100, 85),
 }
 
 
