@@ -576,6 +576,75 @@ int sift_mi_propose_pairs_device(sift_mi_ctx* ctx, const uint8_t* d_desc, const 
  * 1) / 2 a call; cumulative, reset by sift_mi_reset_stats. */
 int sift_mi_pair_counters(sift_mi_ctx* ctx, double* kernel_ms, uint64_t* tiles);
 
+/* ---- spread-limited keypoints (LABELLED EXTENSION: the crate has nothing like it)
+ * Adaptive non-maximal suppression (Brown, Szeliski, Winder, "Multi-image
+ * matching using multi-scale oriented patches", 2005) on the arena d_kps /
+ * d_desc / offsets[n_segs + 1] that the match and track calls take: up to
+ * `limit` keypoints per segment, spread over the frame, where features_limit
+ * keeps the strongest responses wherever they cluster.  The rule is
+ * tests/select_ref.py's; every output equals it bit for bit.  Segments are
+ * independent.  Within one, for row i (responses and positions as f32):
+ *   Suppressor  row j suppresses row i when r_i < c * r_j: one f32 multiply,
+ *               a strict comparison, 0 < c <= 1 (c == 1: only strictly
+ *               stronger rows).  Rows of equal response never suppress each
+ *               other, and a row never suppresses itself.
+ *   Radius      R2_i = the minimum over its suppressors of
+ *               (x_j - x_i) * (x_j - x_i) + (y_j - y_i) * (y_j - y_i), every
+ *               operation a separately rounded f32 operation (no fused
+ *               multiply-add); +inf without a suppressor.
+ *   Selection   the min(rows, limit) rows with the largest R2, compared as the
+ *               u32 pattern of the f32, the lower row first among equals;
+ *               kept in ascending row order.
+ * sel_offsets[n_segs + 1] receives the kept rows' segment bounds, rows[cap]
+ * the kept rows, each relative to its segment's first row (what maps a match
+ * on the compact arena back to the original keypoint), radius2 (may be null)
+ * R2 of every row from offsets[0] to offsets[n_segs].  The kept keypoints and,
+ * when d_desc is not null, their descriptors are gathered into a compact arena
+ * in device memory in the same layout (sift_mi_selected_results): with
+ * sel_offsets it goes straight into sift_mi_match_pairs_device,
+ * sift_mi_verify_pairs_device, sift_mi_match_pairs_guided_device,
+ * sift_mi_build_tracks_device and sift_mi_propose_pairs_device.
+ * Inputs are assumed finite with responses >= 0, which holds for what the
+ * extraction emits.  With a NaN, an infinity or a negative response in a
+ * keypoint the call stays memory-safe and deterministic; its result is
+ * otherwise unspecified.
+ * Limits: the distance is 2-D position only, so keypoints of different scales
+ * at one place compete; the keypoints SIFT emits per orientation peak at one
+ * place have equal radii and are kept or cut by row order; `limit` is one
+ * number for all segments.
+ * SIFT_MI_EINVAL, before any device work, for a null argument other than
+ * d_desc / radius2, limit == 0, c NaN or outside (0, 1], decreasing offsets,
+ * rows above 2^31 - 1, a d_kps that is not 4-byte or a d_desc that is not
+ * 16-byte aligned; and for cap < the rows kept (then sel_offsets is written
+ * and sel_offsets[n_segs] is the number needed).  Empty segments give empty
+ * ranges, n_segs == 0 nothing.  Only reads d_kps and d_desc (the extraction's
+ * device results stay valid); no allocation once the context's scratch has
+ * grown to the call's size. */
+typedef struct {
+    uint32_t limit;
+    float c;
+} sift_mi_select_params;
+int sift_mi_select_spread_device(sift_mi_ctx* ctx, const sift_mi_keypoint* d_kps,
+                                 const uint8_t* d_desc /* may be null */, const size_t* offsets, uint32_t n_segs,
+                                 const sift_mi_select_params* params, size_t* sel_offsets /* n_segs + 1 */,
+                                 uint32_t* rows, size_t cap, float* radius2 /* may be null */);
+/* The compact arena of the last select call: *n kept keypoints and their
+ * descriptors (*d_sel_desc null when that call had none) in device memory,
+ * valid until the next select call or sift_mi_destroy.  n == 0 before any. */
+int sift_mi_selected_results(sift_mi_ctx* ctx, const sift_mi_keypoint** d_sel_kps, const uint8_t** d_sel_desc,
+                             size_t* n);
+/* The one-frame host form: kps[n] in host memory, one segment, no
+ * descriptors.  rows[cap] receives the kept rows, *n_rows = min(n, limit)
+ * (the number needed when cap is smaller: SIFT_MI_EINVAL), radius2[n] may be
+ * null. */
+int sift_mi_select_keypoints(sift_mi_ctx* ctx, const sift_mi_keypoint* kps, size_t n,
+                             const sift_mi_select_params* params, uint32_t* rows, size_t cap, size_t* n_rows,
+                             float* radius2 /* may be null */);
+/* Diagnostic: the kernel time of the select calls (two events around the
+ * launch sequence) and the (row, candidate) pair tests they made, the sum of
+ * rows^2 over a call's segments; cumulative, reset by sift_mi_reset_stats. */
+int sift_mi_select_counters(sift_mi_ctx* ctx, double* kernel_ms, uint64_t* pair_tests);
+
 /* ---- the input step before the path ---------------
  * Baseline (SOF0/SOF1) Huffman JPEG, 1 or 3 components -> 8-bit luma, with
  * the arithmetic of the reference's decode: image 0.25.2 `image::open` /
@@ -664,7 +733,10 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        sift_mi_build_tracks_device, sift_mi_track_counters (feature tracks
  *        over the kept matches; sift_mi_track_params, sift_mi_track_obs);
  *        sift_mi_propose_pairs_device, sift_mi_pair_counters (frame pairs
- *        proposed by preemptive matching; sift_mi_pair_params).
+ *        proposed by preemptive matching; sift_mi_pair_params);
+ *        sift_mi_select_spread_device, sift_mi_selected_results,
+ *        sift_mi_select_keypoints, sift_mi_select_counters (spread-limited
+ *        keypoints by adaptive non-maximal suppression; sift_mi_select_params).
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

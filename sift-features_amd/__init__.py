@@ -8,6 +8,7 @@ from .sift import (  # noqa: F401
     DESCRIPTOR_SIZE, Context, ImageprocProcessing, KeyPoint, OpenCVProcessing, PrecomputedImages, Processing,
     ResultBuffers, Tracks, build_tracks_device, track_frames,
     pair_counters, propose_frames, propose_pairs_device,
+    Selection, select_counters, select_frames, select_keypoints, select_spread_device,
     SiftResult, compute_descriptor, decode_jpeg, default_context, jpeg_dims, key_fields, match_descriptors,
     match_frames, match_frames_guided, match_guided, match_neighbors, match_pairs_device, match_pairs_guided_device,
     precompute_images, sift,

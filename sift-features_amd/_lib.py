@@ -28,6 +28,7 @@ EXPORTS = [
     "sift_mi_match_pairs_guided_device", "sift_mi_match_guided", "sift_mi_guided_counters",
     "sift_mi_build_tracks_device", "sift_mi_track_counters",
     "sift_mi_propose_pairs_device", "sift_mi_pair_counters",
+    "sift_mi_select_spread_device", "sift_mi_selected_results", "sift_mi_select_keypoints", "sift_mi_select_counters",
     "sift_mi_decode_jpeg", "sift_mi_decode_jpeg_batch", "sift_mi_get_stats",
     "sift_mi_reset_stats",
     "sift_mi_version", "sift_mi_last_error",
@@ -95,6 +96,11 @@ class PairParams(ctypes.Structure):
     """include/sift_mi.h sift_mi_pair_params."""
     _fields_ = [("subset", ctypes.c_uint32), ("ratio", ctypes.c_float), ("min_matches", ctypes.c_uint32),
                 ("max_partners", ctypes.c_uint32)]
+
+
+class SelectParams(ctypes.Structure):
+    """include/sift_mi.h sift_mi_select_params."""
+    _fields_ = [("limit", ctypes.c_uint32), ("c", ctypes.c_float)]
 
 
 MODEL_KINDS = {"homography": 0, "fundamental": 1}  # include/sift_mi.h sift_mi_model_kind
@@ -182,6 +188,10 @@ def lib():
         "sift_mi_track_counters": [vp, P(f64), P(u64)],
         "sift_mi_propose_pairs_device": [vp, vp, vp, P(sz), u32, P(PairParams), vp, vp, sz, P(sz)],
         "sift_mi_pair_counters": [vp, P(f64), P(u64)],
+        "sift_mi_select_spread_device": [vp, vp, vp, P(sz), u32, P(SelectParams), P(sz), vp, sz, vp],
+        "sift_mi_selected_results": [vp, P(vp), P(vp), P(sz)],
+        "sift_mi_select_keypoints": [vp, vp, sz, P(SelectParams), vp, sz, P(sz), vp],
+        "sift_mi_select_counters": [vp, P(f64), P(u64)],
         "sift_mi_jpeg_dims": [vp, sz, P(u32), P(u32)],
         "sift_mi_decode_jpeg": [vp, vp, sz, vp, sz, i32],
         "sift_mi_decode_jpeg_batch": [vp, P(vp), P(sz), u32, vp, sz, sz, i32],

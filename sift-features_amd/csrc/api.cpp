@@ -8,6 +8,7 @@
 
 #include "host_internal.h"
 #include "pair_propose.h"
+#include "select_rule.h"
 
 using namespace siftmi;
 
@@ -696,6 +697,89 @@ int pairs_run(sift_mi_ctx* c, const uint8_t* d_desc, const OutKp* d_kps, const s
     if (!out.empty()) std::memcpy(pairs, out.data(), out.size() * sizeof(sift_mi_seg_pair));
     return 0;
 }
+
+// Spread-limited selection on device keypoints d_kps (host keypoints h_kps
+// instead when d_kps is null: the one-frame form) and optional device rows
+// d_desc of one arena: every check and sel_offsets on the host first
+// (select_rule.h), then launch_select on the context stream between the two
+// events of sift_mi_select_counters; rows and, if asked for, radius2 come back.
+int select_run(sift_mi_ctx* c, const OutKp* d_kps, const OutKp* h_kps, const uint8_t* d_desc, const size_t* offsets,
+               uint32_t n_segs, const sift_mi_select_params* prm, size_t* sel_offsets, uint32_t* rows, size_t cap,
+               float* radius2) {
+    if (const char* msg = select_params_error(prm->limit, prm->c)) return fail(SIFT_MI_EINVAL, msg);
+    if (const char* msg = select_arena_error(d_kps, d_desc, offsets, n_segs)) return fail(SIFT_MI_EINVAL, msg);
+    select_fill_offsets(offsets, n_segs, prm->limit, sel_offsets);
+    const size_t total = sel_offsets[n_segs];
+    if (cap < total) return fail(SIFT_MI_EINVAL, "cap < number of kept rows (sel_offsets[n_segs])");
+    const size_t row_base = offsets[0], n_rows = offsets[n_segs] - row_base;
+    size_t n_wgs = 0;
+    for (uint32_t s = 0; s < n_segs; s++)
+        n_wgs += (offsets[s + 1] - offsets[s] + kSelectRowsPerWg - 1) / kSelectRowsPerWg;
+
+    CHK(set_device(c));
+    SelectScratch& S = c->select;
+    hipStream_t st = c->stream;
+    S.n_sel = 0;
+    S.has_desc = d_desc != nullptr;
+    if (total == 0) return 0;  // (then no segment has a row)
+    const size_t n_off = (size_t)n_segs + 1, words = 2 * n_off + 2 * n_wgs;
+    CHK(pool(S.h_tab, words));
+    CHK(pool(S.tab, words));
+    CHK(pool(S.r2, n_rows));
+    CHK(pool(S.rows, total));
+    CHK(pool(S.src, total));
+    CHK(pool(S.sel_kps, total));
+    if (d_desc) CHK(pool(S.sel_desc, total * kDescSize));
+    if (h_kps) CHK(pool(S.in_kps, n_rows));
+    if (!S.t0) HIPCHK(hipEventCreate(&S.t0));
+    if (!S.t1) HIPCHK(hipEventCreate(&S.t1));
+    uint32_t* h = S.h_tab.p;
+    uint64_t tests = 0;
+    size_t w = 2 * n_off;
+    for (uint32_t s = 0; s <= n_segs; s++) {
+        h[s] = (uint32_t)(offsets[s] - row_base);
+        h[n_off + s] = (uint32_t)sel_offsets[s];
+    }
+    for (uint32_t s = 0; s < n_segs; s++) {
+        const size_t n = offsets[s + 1] - offsets[s];
+        tests += (uint64_t)n * n;
+        for (size_t r = 0; r < n; r += kSelectRowsPerWg) {
+            h[w++] = s;
+            h[w++] = (uint32_t)r;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(S.tab.p, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (h_kps) HIPCHK(hipMemcpyAsync(S.in_kps.p, h_kps, n_rows * sizeof(OutKp), hipMemcpyHostToDevice, st));
+    SelectLaunch L{};
+    L.kps = h_kps ? S.in_kps.p : d_kps + row_base;
+    L.d = d_desc ? d_desc + row_base * kDescSize : nullptr;
+    L.offs = S.tab.p;
+    L.sel_offs = S.tab.p + n_off;
+    L.wgs = reinterpret_cast<const uint2*>(S.tab.p + 2 * n_off);  // (an even word: 8-byte aligned)
+    L.n_segs = n_segs;
+    L.n_wgs = (uint32_t)n_wgs;
+    L.n_rows = (uint32_t)n_rows;
+    L.total = (uint32_t)total;
+    L.limit = prm->limit;
+    L.c = prm->c;
+    L.r2 = S.r2.p;
+    L.rows = S.rows.p;
+    L.src = S.src.p;
+    L.sel_kps = S.sel_kps.p;
+    L.sel_d = d_desc ? S.sel_desc.p : nullptr;
+    HIPCHK(hipEventRecord(S.t0, st));
+    launch_select(L, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.t1, st));
+    HIPCHK(hipMemcpyAsync(rows, S.rows.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (radius2) HIPCHK(hipMemcpyAsync(radius2, S.r2.p, n_rows * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, S.t0, S.t1) == hipSuccess) S.kernel_ms += ms;
+    S.pair_tests += tests;
+    S.n_sel = total;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1313,6 +1397,49 @@ int sift_mi_pair_counters(sift_mi_ctx* c, double* kernel_ms, uint64_t* tiles) {
     return 0;
 }
 
+// ---- spread-limited selection (labelled extension; select.hip) ------------------
+int sift_mi_select_spread_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const uint8_t* d_desc,
+                                 const size_t* offsets, uint32_t n_segs, const sift_mi_select_params* params,
+                                 size_t* sel_offsets, uint32_t* rows, size_t cap, float* radius2) {
+    if (!c || !d_kps || !offsets || !params || !sel_offsets || !rows) return fail(SIFT_MI_EINVAL, "null argument");
+    return match_guard([&]() -> int {
+        return select_run(c, reinterpret_cast<const OutKp*>(d_kps), nullptr, d_desc, offsets, n_segs, params,
+                          sel_offsets, rows, cap, radius2);
+    });
+}
+
+int sift_mi_selected_results(sift_mi_ctx* c, const sift_mi_keypoint** d_sel_kps, const uint8_t** d_sel_desc,
+                             size_t* n) {
+    if (!c || !d_sel_kps || !d_sel_desc || !n) return fail(SIFT_MI_EINVAL, "null argument");
+    const SelectScratch& S = c->select;
+    *d_sel_kps = reinterpret_cast<const sift_mi_keypoint*>(S.sel_kps.p);
+    *d_sel_desc = S.has_desc ? S.sel_desc.p : nullptr;
+    *n = S.n_sel;
+    return 0;
+}
+
+int sift_mi_select_keypoints(sift_mi_ctx* c, const sift_mi_keypoint* kps, size_t n,
+                             const sift_mi_select_params* params, uint32_t* rows, size_t cap, size_t* n_rows,
+                             float* radius2) {
+    if (!c || !kps || !params || !rows || !n_rows) return fail(SIFT_MI_EINVAL, "null argument");
+    if (n > kSelectMaxRows) return fail(SIFT_MI_EINVAL, "keypoint set too large");
+    return match_guard([&]() -> int {
+        const size_t offsets[2] = {0, n};
+        size_t sel[2] = {0, 0};
+        const int rc = select_run(c, nullptr, reinterpret_cast<const OutKp*>(kps), nullptr, offsets, 1, params, sel,
+                                  rows, cap, radius2);
+        *n_rows = sel[1];
+        return rc;
+    });
+}
+
+int sift_mi_select_counters(sift_mi_ctx* c, double* kernel_ms, uint64_t* pair_tests) {
+    if (!c || !kernel_ms || !pair_tests) return fail(SIFT_MI_EINVAL, "null argument");
+    *kernel_ms = c->select.kernel_ms;
+    *pair_tests = c->select.pair_tests;
+    return 0;
+}
+
 int sift_mi_jpeg_dims(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height) {
     if (!data || !width || !height) return fail(SIFT_MI_EINVAL, "bad arguments");
     return jpeg_guard([&]() -> int {
@@ -1396,6 +1523,8 @@ int sift_mi_reset_stats(sift_mi_ctx* c) {
     c->tracks.edges = 0;
     c->pairs.kernel_ms = 0;
     c->pairs.tiles = 0;
+    c->select.kernel_ms = 0;
+    c->select.pair_tests = 0;
     if (c->samples.p) {
         CHK(set_device(c));
         CHK(sync_lanes(c));

@@ -352,6 +352,28 @@ struct PairScratch {
     }
 };
 
+// Pooled scratch of the spread-limited selection (sift_mi_select_spread_device):
+// grows on demand, freed with the context.  sel_kps / sel_desc are the compact
+// arena sift_mi_selected_results hands out.
+struct SelectScratch {
+    DevBuf<uint32_t> tab;    // offs[n_segs + 1], sel_offs[n_segs + 1], then the radius workgroups' (segment, row)
+    PinBuf<uint32_t> h_tab;  // its host image
+    DevBuf<OutKp> in_kps;    // the one-frame host form's keypoints
+    DevBuf<float> r2;        // per arena row
+    DevBuf<uint32_t> rows, src;
+    DevBuf<OutKp> sel_kps;
+    DevBuf<uint8_t> sel_desc;
+    size_t n_sel = 0;
+    bool has_desc = false;
+    hipEvent_t t0 = nullptr, t1 = nullptr;  // around the kernels
+    double kernel_ms = 0;                   // sift_mi_select_counters
+    uint64_t pair_tests = 0;
+    ~SelectScratch() {
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+    }
+};
+
 }  // namespace siftmi
 
 struct sift_mi_ctx {
@@ -426,6 +448,7 @@ struct sift_mi_ctx {
     siftmi::VerifyScratch verify;
     siftmi::TrackScratch tracks;
     siftmi::PairScratch pairs;
+    siftmi::SelectScratch select;
     sift_mi_stats stats{};
 };
 

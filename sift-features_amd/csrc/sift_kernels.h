@@ -435,6 +435,30 @@ constexpr uint32_t kPairSubsetMax = 128;  // one 128 x 128 tile is a whole frame
 void launch_pairs(const OutKp* kps, const uint8_t* d, const uint32_t* offs, uint32_t n_segs, uint32_t h, float ratio,
                   uint32_t* cnt, uint8_t* sub_d, int* sub_m, uint32_t* score, hipStream_t st);
 
+// select.hip
+// Spread-limited selection by adaptive non-maximal suppression (LABELLED
+// EXTENSION; tests/select_ref.py is the definition).  kps / d: the call's
+// first row (d may be null: no descriptors); offs[n_segs + 1]: the segments'
+// first rows from it; sel_offs[n_segs + 1]: the running sums of min(n_s,
+// limit), total = their last; wgs[n_wgs] = (segment, first query row) of each
+// radius workgroup, kSelectRowsPerWg rows apiece, none of them spanning two
+// segments.  r2[rows of the arena], rows / src[total] and the compact arena
+// sel_kps[total], sel_d[total * 128] (unused when d is null) are written.
+constexpr uint32_t kSelectRowsPerWg = 512;
+struct SelectLaunch {
+    const OutKp* kps;
+    const uint8_t* d;
+    const uint32_t *offs, *sel_offs;
+    const uint2* wgs;
+    uint32_t n_segs, n_wgs, n_rows, total, limit;  // n_rows: the arena's rows, offs[n_segs]
+    float c;
+    float* r2;
+    uint32_t *rows, *src;
+    OutKp* sel_kps;
+    uint8_t* sel_d;
+};
+void launch_select(const SelectLaunch& L, hipStream_t st);
+
 // describe.hip
 // Descriptor work queues: keypoint i belongs to queue i % kDescQueues, which
 // hands out its keypoints in order; 8 counters on separate 128-B lines (one

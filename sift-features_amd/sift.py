@@ -134,6 +134,36 @@ class Tracks:
         return f"Tracks(n={len(self)}, observations={len(self.obs)})"
 
 
+class Selection:
+    """Spread-limited keypoints (Context.select_spread_device; LABELLED
+    EXTENSION).  `offsets` (n_segs + 1,) int64: the kept rows' segment bounds;
+    `rows` (offsets[-1],) uint32: each kept row relative to its segment's first
+    row, ascending within a segment (rows[offsets[s] + k] is what index k of
+    segment s of the compact arena was in the original arena); `radius2` (N,)
+    f32: the squared suppression radius of every input row (inf: nothing
+    suppresses it), or None; `d_kps_ptr` / `d_desc_ptr`: the compact arena in
+    device memory (kept keypoints and descriptors in the input's layout;
+    d_desc_ptr is None when the call had no descriptors), valid until the
+    context's next select call.  With `offsets` they go straight into
+    match_pairs_device, verify_pairs_device and the other arena calls."""
+
+    __slots__ = ("offsets", "rows", "radius2", "d_kps_ptr", "d_desc_ptr")
+
+    def __init__(self, offsets, rows, radius2, d_kps_ptr, d_desc_ptr):
+        self.offsets, self.rows, self.radius2 = offsets, rows, radius2
+        self.d_kps_ptr, self.d_desc_ptr = d_kps_ptr, d_desc_ptr
+
+    def __len__(self):
+        return len(self.rows)
+
+    def segment_rows(self, s):
+        """The kept rows of segment s (relative to its first row)."""
+        return self.rows[self.offsets[s]:self.offsets[s + 1]]
+
+    def __repr__(self):
+        return f"Selection(segments={len(self.offsets) - 1}, kept={len(self.rows)})"
+
+
 def _match_arrays(a, lo, hi):
     """Rows lo..hi of a sift_mi_match record array as (query_idx, train_idx, distance)."""
     a = a[lo:hi]
@@ -746,6 +776,79 @@ class Context:
         check(lib().sift_mi_pair_counters(self._h, ctypes.byref(ms), ctypes.byref(tiles)))
         return {"kernel_ms": ms.value, "tiles": tiles.value}
 
+    # -- spread-limited keypoints (LABELLED EXTENSION: not in the crate) -----------
+    def select_spread_device(self, d_kps_ptr, d_desc_ptr, offsets, limit, c=0.9, radius2=True):
+        """LABELLED EXTENSION: up to `limit` keypoints per segment of a device
+        arena, spread over the frame by adaptive non-maximal suppression
+        (sift_mi_select_spread_device; the rule is tests/select_ref.py's).  A
+        row's squared radius is its unfused f32 squared distance to the
+        nearest row j of its segment with response_i < c * response_j
+        (0 < c <= 1), inf without one; the min(rows, limit) rows with the
+        largest radius are kept (the lower row first among equals), in
+        ascending row order.  d_desc_ptr may be None (keypoints only).
+        Returns a Selection; radius2=False leaves its radius2 None.  Where
+        features_limit keeps the strongest responses wherever they cluster,
+        this keeps the keypoints a homography, a fundamental matrix or a
+        track set wants: all over the frame."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
+            raise ValueError("offsets: n_segs + 1 non-negative row numbers")
+        n = len(offs) - 1
+        limit = int(limit)
+        if not 0 <= limit <= 0xFFFFFFFF:
+            raise ValueError("limit must fit 32 bits")
+        c_offs = (ctypes.c_size_t * len(offs))(*[int(v) for v in offs])
+        sel = (ctypes.c_size_t * len(offs))()
+        lens = np.maximum(np.diff(offs), 0)
+        cap = int(np.minimum(lens, limit).sum())
+        rows = np.zeros(max(cap, 1), np.uint32)
+        r2 = np.zeros(max(int(offs[-1] - offs[0]), 1), np.float32) if radius2 else None
+        prm = _lib.SelectParams(limit, float(c))
+        check(lib().sift_mi_select_spread_device(self._h, ctypes.c_void_p(d_kps_ptr), ctypes.c_void_p(d_desc_ptr),
+                                                 c_offs, n, ctypes.byref(prm), sel, rows.ctypes.data, cap,
+                                                 r2.ctypes.data if radius2 else None))
+        kp, desc, k = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        check(lib().sift_mi_selected_results(self._h, ctypes.byref(kp), ctypes.byref(desc), ctypes.byref(k)))
+        return Selection(np.array(sel[:], dtype=np.int64), rows[:k.value],
+                         r2[:max(int(offs[-1] - offs[0]), 0)] if radius2 else None, kp.value, desc.value)
+
+    def select_frames(self, offsets, limit, c=0.9, radius2=True):
+        """select_spread_device on the results the last
+        sift_batch_device(..., fetch=False) left in HBM (which stay as they
+        are): sel = select_frames(offs, 2000), then e.g.
+        match_pairs_device(sel.d_desc_ptr, sel.offsets, pairs)."""
+        d_kps, d_desc, n = self.device_results()
+        if int(offsets[-1]) > n:
+            raise ValueError("offsets reach beyond the device results")
+        return self.select_spread_device(d_kps, d_desc, offsets, limit, c, radius2)
+
+    def select_keypoints(self, kps, limit, c=0.9):
+        """The one-frame form on host keypoints (sift_mi_select_keypoints):
+        kps an (n, 5) f32 keypoint array (SiftResult.keypoints_array; x, y and
+        response are read).  Returns (rows uint32 ascending, radius2 f32 (n,))."""
+        k = np.ascontiguousarray(kps, dtype=np.float32).reshape(-1, 5)
+        limit = int(limit)
+        if not 0 <= limit <= 0xFFFFFFFF:
+            raise ValueError("limit must fit 32 bits")
+        cap = min(len(k), limit)
+        buf = k if len(k) else np.zeros((1, 5), np.float32)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        r2 = np.zeros(max(len(k), 1), np.float32)
+        n_rows = ctypes.c_size_t()
+        prm = _lib.SelectParams(limit, float(c))
+        check(lib().sift_mi_select_keypoints(self._h, buf.ctypes.data, len(k), ctypes.byref(prm), rows.ctypes.data, cap,
+                                             ctypes.byref(n_rows), r2.ctypes.data))
+        return rows[:n_rows.value], r2[:len(k)]
+
+    def select_counters(self):
+        """{"kernel_ms", "pair_tests"} of the select calls since the last
+        reset_stats(): the time between two events around their launch
+        sequences and the (row, candidate) tests they made, the sum of rows^2
+        over a call's segments (sift_mi_select_counters)."""
+        ms, tests = ctypes.c_double(), ctypes.c_uint64()
+        check(lib().sift_mi_select_counters(self._h, ctypes.byref(ms), ctypes.byref(tests)))
+        return {"kernel_ms": ms.value, "pair_tests": tests.value}
+
     # -- the input step (SURVEY.md 8(f) row 2) ------------------------------
     def decode_jpeg(self, data):
         """Baseline JPEG bytes -> (h, w) u8 luma, as the reference makes its
@@ -1014,6 +1117,27 @@ def propose_frames(offsets, subset=128, ratio=0.8, min_matches=8, max_partners=0
 def pair_counters():
     """LABELLED EXTENSION: Context.pair_counters on the default context."""
     return default_context().pair_counters()
+
+
+def select_spread_device(d_kps_ptr, d_desc_ptr, offsets, limit, c=0.9, radius2=True):
+    """LABELLED EXTENSION: Context.select_spread_device on the default context."""
+    return default_context().select_spread_device(d_kps_ptr, d_desc_ptr, offsets, limit, c, radius2)
+
+
+def select_frames(offsets, limit, c=0.9, radius2=True):
+    """LABELLED EXTENSION: Context.select_frames on the default context (its
+    last sift_batch_device(..., fetch=False) results)."""
+    return default_context().select_frames(offsets, limit, c, radius2)
+
+
+def select_keypoints(kps, limit, c=0.9):
+    """LABELLED EXTENSION: Context.select_keypoints on the default context."""
+    return default_context().select_keypoints(kps, limit, c)
+
+
+def select_counters():
+    """LABELLED EXTENSION: Context.select_counters on the default context."""
+    return default_context().select_counters()
 
 
 def stable_sort_xy_size(keypoints_array):

@@ -2,7 +2,7 @@
 MI355X path.
 
     python sift-features_amd/sift_match.py <a.jpg> <b.jpg> [--ratio R] [--verify [THR]]
-                                           [--model homography|fundamental] [--guided]
+                                           [--model homography|fundamental] [--guided] [--spread N]
                                            [--processing opencv|imageproc] [--device N]
 
 examples/sift-match.rs:30-35, :87-97 opens two images, runs `sift()` on each and
@@ -22,6 +22,11 @@ fundamental matrix instead (verify_epipolar.hip; THR is the Sampson distance).
 the pair again under the fitted model (match_guided.hip, the defaults of
 Context.match_guided: cross check, no ratio test, no distance cap, the
 verification's threshold) and prints a fifth line with the guided match count.
+`--spread N`, a labelled extension as well, keeps at most N keypoints of each
+image, spread over the frame by adaptive non-maximal suppression (select.hip,
+the defaults of Context.select_keypoints), before matching; a further line
+gives the kept counts, and the matches, inliers and guided matches are those
+of the kept keypoints (their indices mapped back to the extraction's rows).
 Exits non-zero (with the library's error) when the HIP library or
 the device is missing: there is no CPU fallback.
 """
@@ -41,6 +46,7 @@ def main(argv=None):
     ap.add_argument("--verify", type=float, nargs="?", const=3.0, default=None, metavar="THR")
     ap.add_argument("--model", choices=["homography", "fundamental"], default="homography")
     ap.add_argument("--guided", action="store_true")
+    ap.add_argument("--spread", type=int, default=None, metavar="N")
     ap.add_argument("--processing", choices=("imageproc", "opencv"), default="imageproc")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
@@ -54,17 +60,25 @@ def main(argv=None):
     ctx = pkg.Context(a.device, proc)
     try:
         res_a, res_b = (ctx.sift_jpeg(d) for d in datas)
-        qi, ti, dist = ctx.match_descriptors(res_b.descriptors, res_a.descriptors, cross_check=True, ratio=a.ratio)
+        kps_a, desc_a, kps_b, desc_b = res_a.keypoints_array, res_a.descriptors, res_b.keypoints_array, res_b.descriptors
+        if a.spread is not None:
+            rows_a, rows_b = (ctx.select_keypoints(k, a.spread)[0] for k in (kps_a, kps_b))
+            kps_a, desc_a, kps_b, desc_b = kps_a[rows_a], desc_a[rows_a], kps_b[rows_b], desc_b[rows_b]
+        qi, ti, dist = ctx.match_descriptors(desc_b, desc_a, cross_check=True, ratio=a.ratio)
         if a.verify is not None:
-            g, _, info = ctx.verify_matches(res_b.keypoints_array, res_a.keypoints_array, (qi, ti, dist),
-                                            threshold=a.verify, model=a.model)
+            g, _, info = ctx.verify_matches(kps_b, kps_a, (qi, ti, dist), threshold=a.verify, model=a.model)
             if a.guided:
-                guided = ctx.match_guided(res_b.descriptors, res_b.keypoints_array, res_a.descriptors,
-                                          res_a.keypoints_array, g, threshold=a.verify, model=a.model)
+                guided = ctx.match_guided(desc_b, kps_b, desc_a, kps_a, g, threshold=a.verify, model=a.model)
+        if a.spread is not None:  # back to the rows of the two extractions
+            qi, ti = rows_b[qi], rows_a[ti]
+            if a.verify is not None and a.guided:
+                guided = (rows_b[guided[0]], rows_a[guided[1]], *guided[2:])
     finally:
         ctx.close()
     print(f"{len(res_a)} keypoints")
     print(f"{len(res_b)} keypoints")
+    if a.spread is not None:
+        print(f"{len(rows_a)} and {len(rows_b)} kept (spread {a.spread})")
     print(f"{len(qi)} matches" + (f" (ratio {a.ratio:g})" if a.ratio is not None else ""))
     if a.verify is not None:
         print(f"{info['n_inliers']} inliers ({a.model}, threshold {a.verify:g})")
