@@ -16,6 +16,59 @@
  * per GPU).  Distinct contexts run concurrently.
  * Ownership: inputs are borrowed for the duration of a call.  Results live
  * in context-owned buffers until the next extraction call or destroy.
+ *
+ * Call sequence.  A context remembers what its last PRODUCING call left, and
+ * that alone decides the return code of a later call; five values:
+ *   where          none | host | device: where the last result's rows are
+ *   n              their number
+ *   pyramid        the planes of sift_mi_precompute are in the context
+ *   batch_readback the last extraction ran as one chunk (one frame, or
+ *                  sift_mi_set_chunk >= its frames, and no restricted row
+ *                  band), so its planes can be read back
+ *   keep           the sift_mi_set_keep_on_device setting
+ * A new context has where = none, n = 0 and the three flags 0.
+ *
+ *   call                              needs            on success
+ *   sift_mi_extract,                  -                where = host, pyramid = 0,
+ *   sift_mi_extract_batch                              batch_readback = the call
+ *     (host frames)                                    ran as one chunk
+ *   sift_mi_extract_batch_device      -                where = keep ? device : host,
+ *                                                      otherwise as above
+ *   sift_mi_precompute                -                pyramid = 1, where = none,
+ *                                                      batch_readback = 0
+ *   sift_mi_sift_with_precomputed     pyramid          where = host, batch_readback
+ *                                                      = 0, pyramid stays
+ *   sift_mi_fetch, sift_mi_fetch_keys where == host    unchanged
+ *   sift_mi_device_results            where == device  unchanged
+ *   sift_mi_octave_dims,              pyramid          unchanged
+ *   sift_mi_read_scale_space,
+ *   sift_mi_read_dog
+ *   sift_mi_batch_octave_dims,        batch_readback   unchanged
+ *   sift_mi_read_batch_scale_space
+ *   sift_mi_set_keep_on_device        -                keep only; where does not move
+ *   sift_mi_set_max_octaves           -                pyramid = 0, batch_readback = 0
+ *
+ *   - A call whose "needs" is unmet returns SIFT_MI_ESTATE and changes nothing.
+ *   - A call refused for its arguments, before any buffer is touched, changes
+ *     nothing: every SIFT_MI_EINVAL of the four producing calls' own argument
+ *     checks (null pointer, zero size, stride < width, a frame above 16384 px,
+ *     too many frames, features_limit while n_bands > 1), and a cap below n in
+ *     the fetch calls.  "needs" is checked before the arguments.
+ *   - A producing call that fails later (the plan was replaced, an arena or a
+ *     stage buffer rewritten: SIFT_MI_ENOMEM, SIFT_MI_EHIP, SIFT_MI_EUNSUPPORTED)
+ *     leaves where = none, pyramid = 0, batch_readback = 0.  The host-frame
+ *     calls and sift_mi_precompute copy their frames to a staging buffer
+ *     before that point: a failure of that copy (a null pointer inside
+ *     `frames` included) changes nothing.
+ *   - Every other call (the remaining setters, the match / verify / track /
+ *     pair / select calls, the JPEG and op-level calls, the statistics) neither
+ *     needs nor changes any of the five.
+ * Where the last result lives is a fact recorded by the call that produced it:
+ * sift_mi_set_keep_on_device chooses the destination of LATER
+ * sift_mi_extract_batch_device calls and nothing else.  Host-frame calls and
+ * sift_mi_sift_with_precomputed always deliver to the host, under either
+ * setting.  (sift-features_amd/csrc/result_state.h is this rule as code;
+ * tests/call_model.py restates it.)
  */
 #ifndef SIFT_MI_H
 #define SIFT_MI_H
@@ -100,7 +153,10 @@ int sift_mi_extract(sift_mi_ctx* ctx, const uint8_t* pixels, uint32_t width, uin
 
 /* Copy the last result: `kps[cap]`, `desc[cap * 128]` (row i <-> keypoint i,
  * the (n,128) C-order `Array2<u8>` of SiftResult::descriptors).  Either
- * pointer may be NULL.  cap must be >= the result size. */
+ * pointer may be NULL.  cap must be >= the result size (SIFT_MI_EINVAL).
+ * Needs where == host ("Call sequence" above): SIFT_MI_ESTATE before any
+ * producing call, after sift_mi_precompute, after a failed producing call and
+ * after a device-kept batch, whatever sift_mi_set_keep_on_device says now. */
 int sift_mi_fetch(sift_mi_ctx* ctx, sift_mi_keypoint* kps, uint8_t* desc, size_t cap);
 
 /* Emission keys of the last result, for parity checks: bits
@@ -159,15 +215,23 @@ int sift_mi_set_pipeline_lanes(sift_mi_ctx* ctx, int lanes);
  * merge.  Default band 0 of 1 (the whole frame). */
 int sift_mi_set_row_band(sift_mi_ctx* ctx, uint32_t band, uint32_t n_bands);
 
-/* Skip the device->host copy of results in batch calls (results stay in
- * device memory; see sift_mi_device_results).  Default 0 = copy. */
+/* Skip the device->host copy of results in later
+ * sift_mi_extract_batch_device calls (their results stay in device memory;
+ * see sift_mi_device_results).  Default 0 = copy.  Only a setting: the last
+ * result stays where its call put it, and sift_mi_fetch /
+ * sift_mi_device_results go on answering for that call.  Host-frame calls
+ * (sift_mi_extract, sift_mi_extract_batch) and sift_mi_sift_with_precomputed
+ * deliver to the host under either value. */
 int sift_mi_set_keep_on_device(sift_mi_ctx* ctx, int keep);
 
-/* Device pointers of the last batch's results (keep_on_device = 1): the
+/* Device pointers of the last result, when a sift_mi_extract_batch_device
+ * call under keep_on_device = 1 produced it (where == device, "Call sequence"
+ * above; SIFT_MI_ESTATE otherwise, with the outputs untouched): the
  * keypoints and descriptors of every frame, concatenated in frame order
- * (frame i at offsets[i] .. offsets[i+1]); valid until the next extraction
- * call (or precompute / destroy): the match calls only read them, so
- * several sift_mi_match_pairs_device calls may follow one extraction. */
+ * (frame i at offsets[i] .. offsets[i+1]); valid until the next producing
+ * call (extraction, precompute, sift_with_precomputed) or destroy: the match
+ * calls only read them, so several sift_mi_match_pairs_device calls may
+ * follow one extraction. */
 int sift_mi_device_results(sift_mi_ctx* ctx, const sift_mi_keypoint** d_kps, const uint8_t** d_desc, size_t* n);
 
 /* Validation read-back (extension, not the crate): the Gaussian planes
@@ -175,9 +239,11 @@ int sift_mi_device_results(sift_mi_ctx* ctx, const sift_mi_keypoint** d_kps, con
  * call, as that call's pyramid left them in the context's arena -- (6, h, w)
  * f32 like sift_mi_read_scale_space, with (w, h) from
  * sift_mi_batch_octave_dims; `out_floats` is the capacity of `out`
- * (SIFT_MI_EINVAL below 6 * w * h).  Valid only when the last call ran as
- * one chunk (one frame, or sift_mi_set_chunk >= its frames) and until the
- * next call of any kind (precompute included); SIFT_MI_ESTATE otherwise.
+ * (SIFT_MI_EINVAL below 6 * w * h).  Valid only when the last extraction ran
+ * as one chunk (one frame, or sift_mi_set_chunk >= its frames) and until the
+ * next producing call (precompute and sift_with_precomputed included) or
+ * sift_mi_set_max_octaves: batch_readback of "Call sequence" above;
+ * SIFT_MI_ESTATE otherwise.
  * Lets tests check the batch path's planes (which no DoG is materialised
  * for) against precompute_images. */
 int sift_mi_batch_octave_dims(sift_mi_ctx* ctx, size_t octave, uint32_t* width, uint32_t* height);
@@ -229,12 +295,17 @@ int sift_mi_set_path_option(sift_mi_ctx* ctx, int option, int value);
 /* ---- src/lib.rs:123-143 `precompute_images` / `PrecomputedImages` ------- */
 int sift_mi_precompute(sift_mi_ctx* ctx, const uint8_t* pixels, uint32_t width, uint32_t height,
                        size_t row_stride, size_t* n_octaves);
+/* The three read calls need `pyramid` of "Call sequence" above (SIFT_MI_ESTATE). */
 int sift_mi_octave_dims(sift_mi_ctx* ctx, size_t octave, uint32_t* width, uint32_t* height);
 /* scale_space[octave]: (6, h, w) f32; dog[octave]: (5, h, w) f32 */
 int sift_mi_read_scale_space(sift_mi_ctx* ctx, size_t octave, float* out);
 int sift_mi_read_dog(sift_mi_ctx* ctx, size_t octave, float* out);
 
-/* ---- src/lib.rs:147 `sift_with_precomputed(&PrecomputedImages, limit)` -- */
+/* ---- src/lib.rs:147 `sift_with_precomputed(&PrecomputedImages, limit)` --
+ * On the planes of the last sift_mi_precompute (SIFT_MI_ESTATE when an
+ * extraction, sift_mi_set_max_octaves or a failed call has ended them);
+ * the result goes to the host: fetch with sift_mi_fetch.  May be called
+ * repeatedly on one precompute. */
 int sift_mi_sift_with_precomputed(sift_mi_ctx* ctx, int64_t features_limit, size_t* n_keypoints);
 
 /* ---- src/lib.rs:785 `compute_descriptor(img, x, y, scale, orientation)` -
@@ -737,6 +808,10 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        sift_mi_select_spread_device, sift_mi_selected_results,
  *        sift_mi_select_keypoints, sift_mi_select_counters (spread-limited
  *        keypoints by adaptive non-maximal suppression; sift_mi_select_params).
+ *        The call-sequence contract at the top of this file (no symbol
+ *        changed): sift_mi_fetch / sift_mi_device_results answer for the call
+ *        that produced the last result, not for the current keep_on_device
+ *        setting; a refused or failed call leaves what the contract says.
  * 0.4.0: sift_mi_set_path_option (replaces the environment knobs),
  *        sift_mi_batch_octave_dims, sift_mi_read_batch_scale_space takes the
  *        output capacity, sift_mi_stats gained pyramid_scan_bytes (pyramid_bytes

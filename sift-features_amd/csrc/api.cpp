@@ -881,7 +881,7 @@ int sift_mi_set_max_octaves(sift_mi_ctx* c, int max_octaves) {
     CHK(set_device(c));
     CHK(sync_lanes(c));
     c->max_octaves = max_octaves;  // the plan is rebuilt on the next call
-    c->have_pyramid = false;
+    c->rs.set_max_octaves();
     return 0;
 }
 
@@ -936,7 +936,7 @@ int sift_mi_set_path_option(sift_mi_ctx* c, int option, int value) {
 
 int sift_mi_set_keep_on_device(sift_mi_ctx* c, int keep) {
     if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
-    c->keep_on_device = keep ? 1 : 0;
+    c->rs.set_keep(keep != 0);  // the destination of later device-frame calls; the last result stays where it is
     return 0;
 }
 
@@ -944,21 +944,19 @@ int sift_mi_extract_batch_device(sift_mi_ctx* c, const uint8_t* d_frames, size_t
                                  uint32_t w, uint32_t h, size_t stride, int64_t limit, size_t* offsets) {
     if (!c || !d_frames || n == 0) return fail(SIFT_MI_EINVAL, "bad arguments");
     if (frame_pitch < stride * (h - 1) + w && n > 1) return fail(SIFT_MI_EINVAL, "frame_pitch too small");
+    CHK(check_extract_args(c, n, w, h, stride, limit));
     CHK(set_device(c));
-    return extract_device(c, d_frames, frame_pitch, n, w, h, stride, limit, offsets);
+    return extract_device(c, ProducingCall::extract_device, d_frames, frame_pitch, n, w, h, stride, limit, offsets);
 }
 
 int sift_mi_extract_batch(sift_mi_ctx* c, const uint8_t* const* frames, uint32_t n, uint32_t w, uint32_t h,
                           size_t stride, int64_t limit, size_t* offsets) {
     if (!c || !frames || n == 0) return fail(SIFT_MI_EINVAL, "bad arguments");
-    CHK(check_frame_args(w, h, stride));
+    CHK(check_extract_args(c, n, w, h, stride, limit));  // before the staging buffer is written
     CHK(set_device(c));
     CHK(upload_frames(c, frames, n, w, h, stride));
-    const int keep = c->keep_on_device;
-    c->keep_on_device = 0;
-    const int rc = extract_device(c, c->staging.p, (size_t)w * h, n, w, h, w, limit, offsets);
-    c->keep_on_device = keep;
-    return rc;
+    // host frames: the rows go to the host whatever the keep setting says
+    return extract_device(c, ProducingCall::extract, c->staging.p, (size_t)w * h, n, w, h, w, limit, offsets);
 }
 
 int sift_mi_extract(sift_mi_ctx* c, const uint8_t* pixels, uint32_t w, uint32_t h, size_t stride, int64_t limit,
@@ -973,31 +971,33 @@ int sift_mi_extract(sift_mi_ctx* c, const uint8_t* pixels, uint32_t w, uint32_t 
 
 int sift_mi_fetch(sift_mi_ctx* c, sift_mi_keypoint* kps, uint8_t* desc, size_t cap) {
     if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
-    if (!c->have_result || c->keep_on_device) return fail(SIFT_MI_ESTATE, "no host result to fetch");
-    if (cap < c->n_result) return fail(SIFT_MI_EINVAL, "cap < result size");
+    if (!c->rs.can_fetch()) return fail(SIFT_MI_ESTATE, "no host result to fetch");
+    const size_t n = c->rs.n;
+    if (cap < n) return fail(SIFT_MI_EINVAL, "cap < result size");
     static_assert(sizeof(sift_mi_keypoint) == sizeof(OutKp), "layout");
-    if (kps && c->n_result) par_memcpy(kps, c->h_kp.p, c->n_result * sizeof(OutKp));
-    if (desc && c->n_result) par_memcpy(desc, c->h_desc.p, c->n_result * kDescSize);
+    if (kps && n) par_memcpy(kps, c->h_kp.p, n * sizeof(OutKp));
+    if (desc && n) par_memcpy(desc, c->h_desc.p, n * kDescSize);
     return 0;
 }
 
 int sift_mi_fetch_keys(sift_mi_ctx* c, uint64_t* keys, size_t cap) {
     if (!c || !keys) return fail(SIFT_MI_EINVAL, "bad arguments");
-    if (!c->have_result || c->keep_on_device) return fail(SIFT_MI_ESTATE, "no host result to fetch");
-    if (cap < c->n_result) return fail(SIFT_MI_EINVAL, "cap < result size");
-    if (c->n_result) par_memcpy(keys, c->h_key.p, c->n_result * sizeof(uint64_t));
+    if (!c->rs.can_fetch()) return fail(SIFT_MI_ESTATE, "no host result to fetch");
+    if (cap < c->rs.n) return fail(SIFT_MI_EINVAL, "cap < result size");
+    if (c->rs.n) par_memcpy(keys, c->h_key.p, c->rs.n * sizeof(uint64_t));
     return 0;
 }
 
 int sift_mi_device_results(sift_mi_ctx* c, const sift_mi_keypoint** d_kps, const uint8_t** d_desc, size_t* n) {
     if (!c) return fail(SIFT_MI_EINVAL, "ctx is null");
-    if (!c->have_result) return fail(SIFT_MI_ESTATE, "no result");
-    if (!c->keep_on_device) return fail(SIFT_MI_ESTATE, "results were copied to the host (keep_on_device is 0)");
+    if (!c->rs.can_device_results())
+        return fail(SIFT_MI_ESTATE, c->rs.where == ResultWhere::host ? "the last result was copied to the host"
+                                                                     : "no device result");
     const bool direct = c->res_slot >= 0;
     const Slot& S = c->slot[direct ? c->res_slot : 0];
     if (d_kps) *d_kps = reinterpret_cast<const sift_mi_keypoint*>(direct ? S.out_kp.p : c->r_kp.p);
     if (d_desc) *d_desc = direct ? S.out_desc.p : c->r_desc.p;
-    if (n) *n = c->n_result;
+    if (n) *n = c->rs.n;
     return 0;
 }
 
@@ -1008,36 +1008,37 @@ int sift_mi_precompute(sift_mi_ctx* c, const uint8_t* pixels, uint32_t w, uint32
     CHK(check_frame_args(w, h, stride));
     CHK(set_device(c));
     const uint8_t* frames[1] = {pixels};
-    c->batch_arena = -1;  // arena 0 is rewritten: the last batch's planes are gone
     CHK(upload_frames(c, frames, 1, w, h, stride));
+    // the plan may be replaced and arena 0 is rewritten: an earlier pyramid, the
+    // last batch's planes and the last result go, also when this call fails
+    ProducingScope<> scope(c->rs);
     CHK(ensure_plan(c, w, h, 1));
     CHK(run_pyramid(c, 0, c->staging.p, (size_t)w * h, w, 1, true));
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->have_pyramid = true;
-    c->have_result = false;
+    scope.done(ProducingCall::precompute, ResultWhere::none, 0, false);
     if (n_octaves) *n_octaves = (size_t)c->plan.n_oct;
     return 0;
 }
 
 int sift_mi_octave_dims(sift_mi_ctx* c, size_t o, uint32_t* w, uint32_t* h) {
-    if (!c || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    if (!c || !c->rs.can_read_pyramid()) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
     return octave_dims(c->plan, o, w, h);
 }
 
 int sift_mi_read_scale_space(sift_mi_ctx* c, size_t o, float* out) {
-    if (!c || !out || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    if (!c || !out || !c->rs.can_read_pyramid()) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
     if (o >= (size_t)c->plan.n_oct) return fail(SIFT_MI_EINVAL, "octave out of range");
     CHK(set_device(c));
     return read_planes(c->plan, (int)o, c->plan.gauss((int)o), kImagesPerOctave, out);
 }
 
 int sift_mi_batch_octave_dims(sift_mi_ctx* c, size_t o, uint32_t* w, uint32_t* h) {
-    if (!c || c->batch_arena < 0) return fail(SIFT_MI_ESTATE, "no single-chunk batch pyramid");
+    if (!c || !c->rs.can_read_batch()) return fail(SIFT_MI_ESTATE, "no single-chunk batch pyramid");
     return octave_dims(c->plan, o, w, h);
 }
 
 int sift_mi_read_batch_scale_space(sift_mi_ctx* c, uint32_t frame, size_t o, float* out, size_t out_floats) {
-    if (!c || !out || c->batch_arena < 0) return fail(SIFT_MI_ESTATE, "no single-chunk batch pyramid");
+    if (!c || !out || !c->rs.can_read_batch()) return fail(SIFT_MI_ESTATE, "no single-chunk batch pyramid");
     Plan& p = c->plan;
     if (o >= (size_t)p.n_oct || frame >= c->batch_frames || frame >= p.chunk)
         return fail(SIFT_MI_EINVAL, "frame / octave out of range");
@@ -1050,23 +1051,22 @@ int sift_mi_read_batch_scale_space(sift_mi_ctx* c, uint32_t frame, size_t o, flo
 }
 
 int sift_mi_read_dog(sift_mi_ctx* c, size_t o, float* out) {
-    if (!c || !out || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    if (!c || !out || !c->rs.can_read_pyramid()) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
     if (o >= (size_t)c->plan.n_oct) return fail(SIFT_MI_EINVAL, "octave out of range");
     CHK(set_device(c));
     return read_planes(c->plan, (int)o, c->plan.dog((int)o), kDogPerOctave, out);
 }
 
 int sift_mi_sift_with_precomputed(sift_mi_ctx* c, int64_t limit, size_t* n_keypoints) {
-    if (!c || !c->have_pyramid) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    if (!c || !c->rs.can_begin(ProducingCall::with_precomputed)) return fail(SIFT_MI_ESTATE, "no precomputed pyramid");
+    CHK(check_band_limit(c, limit));  // refused for its arguments: nothing changes
     CHK(set_device(c));
-    c->batch_arena = -1;  // a later call: the batch read-back is no longer valid
-    const int keep = c->keep_on_device;
-    c->keep_on_device = 0;
+    // the stage and result buffers are rewritten (the planes are only read)
+    ProducingScope<> scope(c->rs);
+    c->call_dest = c->rs.destination(ProducingCall::with_precomputed);
     size_t offs[2];
-    const int rc = run_chunk_sync(c, nullptr, 0, 0, 1, limit, false, offs);
-    c->keep_on_device = keep;
-    CHK(rc);
-    c->have_result = true;
+    CHK(run_chunk_sync(c, nullptr, 0, 0, 1, limit, false, offs));
+    scope.done(ProducingCall::with_precomputed, c->call_dest, offs[1], false);
     if (n_keypoints) *n_keypoints = offs[1];
     return 0;
 }

@@ -14,6 +14,7 @@
 
 #include "../../include/sift_mi.h"
 #include "geometry.h"
+#include "result_state.h"
 #include "sift_common.h"
 #include "sift_kernels.h"
 
@@ -393,7 +394,6 @@ struct sift_mi_ctx {
     hipEvent_t fork = nullptr;     // orders lane 1 after / before the caller's stream
     int lanes = 2;                 // pipeline lanes (sift_mi_set_pipeline_lanes)
     uint32_t chunk_override = 0;
-    int keep_on_device = 0;
     uint32_t band_r = 0, band_n = 1;  // row band of the keypoint stages (sift_mi_set_row_band)
     siftmi::JpegBatchCache jpeg;      // sift_mi_decode_jpeg_batch buffers
     siftmi::DevBuf<uint32_t> band_flag;  // a refinement left the restricted rows (row bands)
@@ -417,11 +417,14 @@ struct sift_mi_ctx {
     siftmi::PinBuf<siftmi::OutKp> h_kp;
     siftmi::PinBuf<uint8_t> h_desc;
     siftmi::PinBuf<uint64_t> h_key;
-    size_t n_result = 0;
-    bool have_result = false;
-    bool have_pyramid = false;  // single-frame precompute state
-    int res_slot = -1;  // >= 0: the last call's device results are that slot's outputs (one chunk, no copy)
-    int batch_arena = -1;     // >= 0: the last batch call ran as one chunk in this arena (read-back)
+    // What the last producing call left and which calls may read it (result_state.h;
+    // include/sift_mi.h "Call sequence").  The fields below it are details of a
+    // state it admits, never consulted on their own.
+    siftmi::ResultState rs;
+    siftmi::ResultWhere call_dest = siftmi::ResultWhere::host;  // the call in progress: where its rows go
+    size_t n_rows = 0;        // the call in progress: rows emitted so far (finalize_chunk)
+    int res_slot = -1;        // rs.where == device: >= 0, that slot's outputs are the results (one chunk, no copy)
+    int batch_arena = 0;      // rs.batch_readback: the arena the one chunk ran in
     // Single-chunk calls as a HIP graph (PathOpts::graph): the call's ~40
     // launches are captured the second time an identical call (same frames
     // pointer, geometry, bounds, modes, buffers) is seen, then replayed with
@@ -443,7 +446,7 @@ struct sift_mi_ctx {
     uint32_t g_fused = 0;
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
-    uint32_t batch_frames = 0;
+    uint32_t batch_frames = 0;  // rs.batch_readback: its frames
     siftmi::MatchScratch match;
     siftmi::VerifyScratch verify;
     siftmi::TrackScratch tracks;
@@ -461,6 +464,10 @@ constexpr uint32_t kMaxChunk = 256;  // frames per chunk (one workgroup plans th
 int sync_lanes(sift_mi_ctx* c);
 int set_device(sift_mi_ctx* c);
 int check_frame_args(uint32_t w, uint32_t h, size_t stride);
+// Every reason to refuse an extraction for its arguments, before a buffer is touched
+int check_extract_args(const sift_mi_ctx* c, uint32_t n, uint32_t w, uint32_t h, size_t stride, int64_t limit);
+// features_limit under row bands (sift_mi_set_row_band)
+int check_band_limit(const sift_mi_ctx* c, int64_t limit);
 int upload_frames(sift_mi_ctx* c, const uint8_t* const* frames, uint32_t n, uint32_t w, uint32_t h, size_t stride);
 int ensure_plan(sift_mi_ctx* c, uint32_t w, uint32_t h, uint32_t chunk);
 // Stage 1: Gaussian scale space (+ DoG when `full`) of n device-resident u8 frames
@@ -469,9 +476,10 @@ int run_pyramid(sift_mi_ctx* c, int lane, const uint8_t* d_frames, size_t frame_
 // Single chunk, synchronous (sift_with_precomputed)
 int run_chunk_sync(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, size_t stride, uint32_t m,
                    int64_t limit, bool pyramid, size_t* offsets);
-// Device-resident batch pipeline
-int extract_device(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, uint32_t n, uint32_t w, uint32_t h,
-                   size_t stride, int64_t limit, size_t* offsets);
+// Device-resident batch pipeline; `call` says whose frames these are (host frames
+// staged by the caller, or the caller's device frames: result_state.h)
+int extract_device(sift_mi_ctx* c, ProducingCall call, const uint8_t* d_frames, size_t frame_pitch, uint32_t n,
+                   uint32_t w, uint32_t h, size_t stride, int64_t limit, size_t* offsets);
 
 }  // namespace siftmi
 #pragma GCC visibility pop

@@ -844,7 +844,8 @@ int finalize_chunk(sift_mi_ctx* c, int si, size_t* offsets, bool only_chunk = fa
     }
     const uint32_t n_out = h[L.out()];
     accumulate_times(c, S);
-    const size_t base = c->n_result, need = base + n_out;
+    const size_t base = c->n_rows, need = base + n_out;
+    const bool to_device = c->call_dest == ResultWhere::device;
     if (offsets) {
         size_t acc = base;
         for (uint32_t f = 0; f < m; f++) {
@@ -853,11 +854,11 @@ int finalize_chunk(sift_mi_ctx* c, int si, size_t* offsets, bool only_chunk = fa
         }
     }
     c->res_slot = -1;
-    if (c->keep_on_device && only_chunk) {
+    if (to_device && only_chunk) {
         // the call's only chunk: its outputs ARE the batch's device results
         // (valid until the next call, sift_mi_device_results) -- no copy
         c->res_slot = si;
-    } else if (c->keep_on_device) {
+    } else if (to_device) {
         // whole-batch device arena: device-to-device copies on the copy stream
         if (n_out && (need > c->r_kp.cap || need * kDescSize > c->r_desc.cap || need > c->r_key.cap)) {
             HIPCHK(hipStreamSynchronize(c->cstream));
@@ -875,7 +876,7 @@ int finalize_chunk(sift_mi_ctx* c, int si, size_t* offsets, bool only_chunk = fa
         }
         if (n_out) CHK(copy_results(c, S, c->h_kp.p, c->h_desc.p, c->h_key.p, base, n_out, hipMemcpyDeviceToHost));
     }
-    c->n_result = need;
+    c->n_rows = need;
     c->stats.extrema += h1 + hb1;
     c->stats.keypoints += n_out;
     c->stats.frames += m;
@@ -912,7 +913,7 @@ int enqueue_single_graph(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_p
     k.bcb = S.bcb;
     k.limit = limit;
     k.gen = g_alloc_gen.load();
-    k.keep = c->keep_on_device;
+    k.keep = c->call_dest == ResultWhere::device;
     k.exact = c->exact_descriptors;
     k.samples = c->count_samples;
     k.lanes = c->lanes;
@@ -985,7 +986,8 @@ int ensure_plan(sift_mi_ctx* c, uint32_t w, uint32_t h, uint32_t chunk) {
     Plan& p = c->plan;
     const bool same = p.w == w && p.h == h && p.profile == (int)c->profile && p.max_oct == c->max_octaves;
     if (same && p.chunk >= chunk && p.arena[0].p) return 0;
-    c->batch_arena = -1;  // the arenas are re-sized or re-planned: no batch read-back
+    // the arenas are re-sized or re-planned: the caller is a producing call
+    // (ProducingScope), which no earlier pyramid or batch read-back survives
     if (!same) {
         p = Plan{};  // nothing of the old plan is kept
         // per-frame stage high-water marks belong to a frame size
@@ -1102,15 +1104,14 @@ int run_pyramid(sift_mi_ctx* c, int lane, const uint8_t* d_frames, size_t frame_
 
 int run_chunk_sync(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, size_t stride, uint32_t m,
                    int64_t limit, bool pyramid, size_t* offsets) {
-    c->n_result = 0;
-    if (c->band_n > 1 && limit >= 0)
-        return fail(SIFT_MI_EINVAL, "features_limit ranks a whole frame's keypoints: apply it after merging row bands");
+    CHK(check_band_limit(c, limit));  // (the caller has checked it before touching anything)
+    c->n_rows = 0;
     for (int attempt = 0; attempt < 4; attempt++) {
         CHK(enqueue_chunk(c, 0, d_frames, frame_pitch, stride, m, limit, 0, pyramid));
         const int rc = finalize_chunk(c, 0, offsets);
         if (rc < 0) return rc;
         if (rc == 0) {
-            if (offsets) offsets[m] = c->n_result;
+            if (offsets) offsets[m] = c->n_rows;
             HIPCHK(hipStreamSynchronize(c->cstream));
             return 0;
         }
@@ -1123,18 +1124,30 @@ int run_chunk_sync(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, 
 // octaves, sorts and kernel tails of one chunk leave CUs idle that the other
 // fills -- and chunk k+2 is enqueued as soon as chunk k has been finalised.
 // Results travel on the copy stream.
-int extract_device(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, uint32_t n, uint32_t w, uint32_t h,
-                   size_t stride, int64_t limit, size_t* offsets) {
+int check_band_limit(const sift_mi_ctx* c, int64_t limit) {
+    if (c->band_n > 1 && limit >= 0)
+        return fail(SIFT_MI_EINVAL, "features_limit ranks a whole frame's keypoints: apply it after merging row bands");
+    return 0;
+}
+
+int check_extract_args(const sift_mi_ctx* c, uint32_t n, uint32_t w, uint32_t h, size_t stride, int64_t limit) {
     CHK(check_frame_args(w, h, stride));
     if (n > (1u << (64 - kKeyImgShift))) return fail(SIFT_MI_EINVAL, "more than 2^22 frames in one call (key field)");
+    return check_band_limit(c, limit);
+}
+
+namespace {
+// The call proper, after the argument checks; *one_chunk: it ran as one chunk
+// whose planes are whole (the batch read-back).  Calls itself once to redo a
+// row band on the whole-frame pyramid.
+int extract_run(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, uint32_t n, uint32_t w, uint32_t h,
+                size_t stride, int64_t limit, size_t* offsets, bool* one_chunk) {
     const sift_mi_stats stats0 = c->stats;  // restored if a banded pass is redone on the whole pyramid
     unsigned long long samples0[16] = {};   // and the device sample counters with it
     if (c->band_n > 1 && c->count_samples && c->samples.p) {
         CHK(sync_lanes(c));
         HIPCHK(hipMemcpy(samples0, c->samples.p, sizeof samples0, hipMemcpyDeviceToHost));
     }
-    if (c->band_n > 1 && limit >= 0)
-        return fail(SIFT_MI_EINVAL, "features_limit ranks a whole frame's keypoints: apply it after merging row bands");
     double avail = 0;  // device memory this context could hold: free + its own arenas
     if (!c->chunk_override && n > 1) {  // (one frame is one chunk: no query on the latency path)
         size_t free_b = 0, total_b = 0;
@@ -1144,10 +1157,8 @@ int extract_device(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, 
     const uint32_t chunk = std::min(kMaxChunk, c->chunk_override ? std::min(c->chunk_override, n)
                                                                  : auto_chunk(w, h, n, c->opts.chunk_mode, avail));
     CHK(ensure_plan(c, w, h, chunk));
-    c->have_pyramid = false;
-    c->n_result = 0;
-    c->have_result = false;
-    c->batch_arena = -1;
+    c->n_rows = 0;
+    *one_chunk = false;
     if (c->band_n > 1) {
         CHK(c->band_flag.ensure(1));
         HIPCHK(hipMemsetAsync(c->band_flag.p, 0, sizeof(uint32_t), c->stream));
@@ -1200,9 +1211,9 @@ int extract_device(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, 
     // nothing: no synchronisation, whose marker round trip costs a few us)
     if (c->slot[0].pending_copy || c->slot[1].pending_copy) HIPCHK(hipStreamSynchronize(c->cstream));
     for (auto& S2 : c->slot) S2.pending_copy = false;
-    if (offsets) offsets[n] = c->n_result;
-    c->have_result = true;
+    if (offsets) offsets[n] = c->n_rows;
     if (n_chunks == 1 && !c->band_restricted) {
+        *one_chunk = true;
         c->batch_arena = arena_of(c, 0);
         c->batch_frames = n;
     }
@@ -1221,11 +1232,24 @@ int extract_device(sift_mi_ctx* c, const uint8_t* d_frames, size_t frame_pitch, 
             if (c->count_samples && c->samples.p)
                 HIPCHK(hipMemcpy(c->samples.p, samples0, sizeof samples0, hipMemcpyHostToDevice));
             c->band_whole = true;
-            const int rc = extract_device(c, d_frames, frame_pitch, n, w, h, stride, limit, offsets);
+            const int rc = extract_run(c, d_frames, frame_pitch, n, w, h, stride, limit, offsets, one_chunk);
             c->band_whole = false;
             return rc;
         }
     }
+    return 0;
+}
+}  // namespace
+
+int extract_device(sift_mi_ctx* c, ProducingCall call, const uint8_t* d_frames, size_t frame_pitch, uint32_t n,
+                   uint32_t w, uint32_t h, size_t stride, int64_t limit, size_t* offsets) {
+    CHK(check_extract_args(c, n, w, h, stride, limit));  // refused for its arguments: nothing changes
+    // from here on the plan, the arenas and the result buffers are rewritten
+    ProducingScope<> scope(c->rs);
+    c->call_dest = c->rs.destination(call);
+    bool one_chunk = false;
+    CHK(extract_run(c, d_frames, frame_pitch, n, w, h, stride, limit, offsets, &one_chunk));
+    scope.done(call, c->call_dest, c->n_rows, one_chunk);
     return 0;
 }
 
