@@ -459,8 +459,10 @@ int sift_mi_verify_matches(sift_mi_ctx* ctx, const sift_mi_keypoint* query_kps, 
  * not.  Limits: a scene that is one plane (or a camera that only rotates)
  * satisfies a whole family of F, every match of the plane is an inlier of any
  * of them, and the homography call is the right tool there; an eight-match
- * sample is all inliers with probability share^8, so 1024 hypotheses suit
- * inlier shares >= 0.5 and lower shares need more iterations. */
+ * sample is all inliers with probability share^8, so under uniform sampling
+ * 1024 hypotheses suit inlier shares >= 0.5 and lower shares need more
+ * iterations; the *_progressive calls below draw from the best-ranked matches
+ * first and reach lower shares with the same count. */
 typedef struct {
     float    f[9];            /* row-major, largest entry == 1; all 0 if no model */
     uint32_t n_matches;       /* the pair's match count */
@@ -483,6 +485,71 @@ int sift_mi_verify_matches_epipolar(sift_mi_ctx* ctx, const sift_mi_keypoint* qu
                                     const sift_mi_keypoint* train_kps, size_t n_train,
                                     const sift_mi_match* matches, size_t n_matches,
                                     const sift_mi_ransac_params* params, sift_mi_fundamental* model, uint8_t* inliers);
+
+/* LABELLED EXTENSION: the two verifications with progressive sampling (PROSAC:
+ * Chum & Matas, "Matching with PROSAC", CVPR 2005).  Uniform sampling needs
+ * share^k luck per hypothesis (k = 4 for the homography, 8 for the fundamental
+ * matrix); here a pair's matches are ranked by a quality and hypothesis h draws
+ * its sample from the best n_h of them, n_h growing with h, so the early
+ * hypotheses come from the matches most likely to be right.  The rule is stated
+ * in tests/prosac_ref.py, and without refits the result equals that
+ * restatement bit for bit:
+ *   Rank     match i of a pair has the key (u32 pattern of quality[i], i);
+ *            ascending keys: the lower quality value first (a descriptor
+ *            distance: lower is better), the lower index first among equals.
+ *            quality is parallel to matches; null: matches[i].distance.
+ *   Growth   f64, one rounding per operation.  N the pair's match count, T =
+ *            iterations: T_k = T, for i = 0..k-1 T_k = T_k * (k - i) / (N - i);
+ *            T_{n+1} = T_n * (n + 1) / (n + 1 - k); T'_k = 1, T'_{n+1} = T'_n +
+ *            ceil(T_{n+1} - T_n).  The paper fixes T_N at 200 000 draws; here
+ *            T_N is the call's own `iterations`, so the schedule reaches the
+ *            whole set as the call ends (a pair of ten matches is not sampled
+ *            from its top five a thousand times).
+ *   Sample   n_h is the smallest n in [k, N] with h < T'_n: k - 1 distinct
+ *            draws of the uniform calls' scheme below n_h - 1, then rank
+ *            n_h - 1 as the last member.  Without such an n (h >= T'_N, reached
+ *            when N is close to k) the uniform calls' k draws below N, over
+ *            the ranked matches.  The hash is the uniform calls'.
+ * Validity, solve, score, ties, "no model" and the refit rounds are the
+ * uniform calls' on the ranked matches; best_hypothesis is the hypothesis
+ * index, and inliers is in the caller's match order.  The params and result
+ * structs, the other arguments, the checks and the guarantees are those of the
+ * uniform siblings; the calls neither need nor change the call-sequence state.
+ * SIFT_MI_EINVAL in addition, on the host before any device work: a quality
+ * (or, with quality null, a match distance) that is NaN or infinite, or that
+ * has its sign bit set (-0.0 included).
+ * Limits: PROSAC's own stopping criteria are not built, because all hypotheses
+ * of a call run at once.  The ranking counts, per match, the pair's smaller
+ * keys: its cost is the sum over the pairs of N^2 compares, correct for every N
+ * the uniform calls accept and quadratic in it; a sort is the remedy for pairs
+ * of several 10^4 matches. */
+int sift_mi_verify_pairs_progressive_device(sift_mi_ctx* ctx, const sift_mi_keypoint* d_kps, const size_t* offsets,
+                                            uint32_t n_segs, const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                            const sift_mi_match* matches, const size_t* pair_offsets,
+                                            const float* quality /* may be null: matches[i].distance */,
+                                            const sift_mi_ransac_params* params,
+                                            sift_mi_homography* models /* [n_pairs] */,
+                                            uint8_t* inliers /* [pair_offsets[n_pairs]] */);
+int sift_mi_verify_matches_progressive(sift_mi_ctx* ctx, const sift_mi_keypoint* query_kps, size_t n_query,
+                                       const sift_mi_keypoint* train_kps, size_t n_train,
+                                       const sift_mi_match* matches, size_t n_matches,
+                                       const float* quality /* may be null: matches[i].distance */,
+                                       const sift_mi_ransac_params* params, sift_mi_homography* model,
+                                       uint8_t* inliers);
+int sift_mi_verify_pairs_epipolar_progressive_device(sift_mi_ctx* ctx, const sift_mi_keypoint* d_kps,
+                                                     const size_t* offsets, uint32_t n_segs,
+                                                     const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                                     const sift_mi_match* matches, const size_t* pair_offsets,
+                                                     const float* quality /* may be null: matches[i].distance */,
+                                                     const sift_mi_ransac_params* params,
+                                                     sift_mi_fundamental* models /* [n_pairs] */,
+                                                     uint8_t* inliers /* [pair_offsets[n_pairs]] */);
+int sift_mi_verify_matches_epipolar_progressive(sift_mi_ctx* ctx, const sift_mi_keypoint* query_kps, size_t n_query,
+                                                const sift_mi_keypoint* train_kps, size_t n_train,
+                                                const sift_mi_match* matches, size_t n_matches,
+                                                const float* quality /* may be null: matches[i].distance */,
+                                                const sift_mi_ransac_params* params, sift_mi_fundamental* model,
+                                                uint8_t* inliers);
 
 /* LABELLED EXTENSION (the step after the verification): guided matching.  The
  * pairs are matched again like sift_mi_match_pairs_device, but a query
@@ -807,7 +874,12 @@ int sift_mi_set_sample_counting(sift_mi_ctx* ctx, int on);
  *        proposed by preemptive matching; sift_mi_pair_params);
  *        sift_mi_select_spread_device, sift_mi_selected_results,
  *        sift_mi_select_keypoints, sift_mi_select_counters (spread-limited
- *        keypoints by adaptive non-maximal suppression; sift_mi_select_params).
+ *        keypoints by adaptive non-maximal suppression; sift_mi_select_params);
+ *        sift_mi_verify_pairs_progressive_device,
+ *        sift_mi_verify_matches_progressive,
+ *        sift_mi_verify_pairs_epipolar_progressive_device,
+ *        sift_mi_verify_matches_epipolar_progressive (the two verifications
+ *        with quality-ordered PROSAC samples; the uniform calls' structs).
  *        The call-sequence contract at the top of this file (no symbol
  *        changed): sift_mi_fetch / sift_mi_device_results answer for the call
  *        that produced the last result, not for the current keep_on_device

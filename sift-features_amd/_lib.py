@@ -25,6 +25,8 @@ EXPORTS = [
     "sift_mi_match_neighbors", "sift_mi_match_ratio", "sift_mi_match_pairs_device",
     "sift_mi_verify_pairs_device", "sift_mi_verify_matches",
     "sift_mi_verify_pairs_epipolar_device", "sift_mi_verify_matches_epipolar",
+    "sift_mi_verify_pairs_progressive_device", "sift_mi_verify_matches_progressive",
+    "sift_mi_verify_pairs_epipolar_progressive_device", "sift_mi_verify_matches_epipolar_progressive",
     "sift_mi_match_pairs_guided_device", "sift_mi_match_guided", "sift_mi_guided_counters",
     "sift_mi_build_tracks_device", "sift_mi_track_counters",
     "sift_mi_propose_pairs_device", "sift_mi_pair_counters",
@@ -180,6 +182,12 @@ def lib():
         "sift_mi_verify_matches": [vp, vp, sz, vp, sz, vp, sz, P(RansacParams), vp, vp],
         "sift_mi_verify_pairs_epipolar_device": [vp, vp, P(sz), u32, vp, u32, vp, P(sz), P(RansacParams), vp, vp],
         "sift_mi_verify_matches_epipolar": [vp, vp, sz, vp, sz, vp, sz, P(RansacParams), vp, vp],
+        "sift_mi_verify_pairs_progressive_device": [vp, vp, P(sz), u32, vp, u32, vp, P(sz), vp, P(RansacParams), vp,
+                                                    vp],
+        "sift_mi_verify_matches_progressive": [vp, vp, sz, vp, sz, vp, sz, vp, P(RansacParams), vp, vp],
+        "sift_mi_verify_pairs_epipolar_progressive_device": [vp, vp, P(sz), u32, vp, u32, vp, P(sz), vp,
+                                                             P(RansacParams), vp, vp],
+        "sift_mi_verify_matches_epipolar_progressive": [vp, vp, sz, vp, sz, vp, sz, vp, P(RansacParams), vp, vp],
         "sift_mi_match_pairs_guided_device": [vp, vp, vp, P(sz), u32, vp, u32, i32, vp, P(GuidedParams), vp, sz, P(sz)],
         "sift_mi_match_guided": [vp, vp, vp, sz, vp, vp, sz, i32, vp, P(GuidedParams), vp, sz, P(sz)],
         "sift_mi_guided_counters": [vp, P(u64), P(u64)],

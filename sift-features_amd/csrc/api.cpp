@@ -8,6 +8,7 @@
 
 #include "host_internal.h"
 #include "pair_propose.h"
+#include "prosac_growth.h"
 #include "select_rule.h"
 
 using namespace siftmi;
@@ -439,10 +440,16 @@ int check_ransac(const sift_mi_ransac_params* p) {
 // h_query / h_train of the two segments), runs the launch sequence on the context
 // stream and returns once models / inliers are written.  `models` receives
 // n_pairs sift_mi_homography or sift_mi_fundamental records (one layout).
+// sampling Progressive: the qualities (`quality`, or with it null the matches'
+// distance) are checked on the host as well, the growth table of every pair and
+// the ranking gather's workgroup list are built in pinned scratch and uploaded.
+enum class VerifySampling { Uniform, Progressive };
+
 int verify_run(sift_mi_ctx* c, VerifyKind kind, const OutKp* d_kps, const size_t* offsets, uint32_t n_segs,
                const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
                const size_t* pair_offsets, const sift_mi_ransac_params* prm, void* models,
-               uint8_t* inliers, const OutKp* h_query = nullptr, const OutKp* h_train = nullptr) {
+               uint8_t* inliers, const OutKp* h_query = nullptr, const OutKp* h_train = nullptr,
+               VerifySampling sampling = VerifySampling::Uniform, const float* quality = nullptr) {
     constexpr size_t kMax = 0x7fffffff;
     CHK(check_ransac(prm));
     if (((uintptr_t)d_kps & 3) != 0) return fail(SIFT_MI_EINVAL, "d_kps must be 4-byte aligned");
@@ -475,9 +482,38 @@ int verify_run(sift_mi_ctx* c, VerifyKind kind, const OutKp* d_kps, const size_t
         P[p] = VerifyPair{(uint32_t)(pair_offsets[p] - m_base), (uint32_t)(pair_offsets[p + 1] - pair_offsets[p]),
                           (uint32_t)(offsets[qs] - row_base), (uint32_t)(offsets[ts] - row_base)};
     }
+    const bool progressive = sampling == VerifySampling::Progressive;
+    size_t n_wgs = 0;
+    if (progressive) {
+        const int bad = !total ? 0
+                        : quality ? prosac::check_quality(quality + m_base, sizeof(float), total)
+                                  : prosac::check_quality(&matches[m_base].distance, sizeof(sift_mi_match), total);
+        if (bad)
+            return fail(SIFT_MI_EINVAL, std::string(quality ? "quality" : "match distance") +
+                                            (bad == 1 ? " must be finite" : " must have its sign bit clear"));
+        for (uint32_t p = 0; p < n_pairs; p++) n_wgs += (P[p].m + kVerifyRankRows - 1) / kVerifyRankRows;
+        if (n_wgs > kMax) return fail(SIFT_MI_EINVAL, "pairs x matches too large");
+    }
 
     CHK(set_device(c));
     VerifyScratch& V = c->verify;
+    VerifyProgressive prog{};
+    if (progressive) {
+        const uint32_t k = kind == VerifyKind::Fundamental ? 8 : 4;
+        CHK(pool(V.growth, total));
+        CHK(pool(V.perm, total));
+        CHK(pool(V.rank_wgs, n_wgs));
+        if (quality) CHK(pool(V.quality, total));
+        CHK(V.h_growth.ensure(total));
+        CHK(V.h_rank_wgs.ensure(n_wgs));
+        prosac::fill_tables(
+            n_pairs, [&P](size_t p, uint32_t& m, uint32_t& first) { m = P[p].m, first = P[p].rec0; }, k,
+            prm->iterations, V.h_growth.p);
+        size_t w = 0;
+        for (uint32_t p = 0; p < n_pairs; p++)
+            for (uint32_t r = 0; r < P[p].m; r += kVerifyRankRows) V.h_rank_wgs.p[w++] = make_uint2(p, r);
+        prog = VerifyProgressive{quality ? V.quality.p : nullptr, V.growth.p, V.rank_wgs.p, (uint32_t)n_wgs, V.perm.p};
+    }
     CHK(pool(V.pairs, n_pairs));
     CHK(pool(V.matches, total));
     CHK(pool(V.rec, total));
@@ -497,14 +533,21 @@ int verify_run(sift_mi_ctx* c, VerifyKind kind, const OutKp* d_kps, const size_t
     HIPCHK(hipMemcpyAsync(V.pairs.p, P.data(), (size_t)n_pairs * sizeof(VerifyPair), hipMemcpyHostToDevice, st));
     if (total)
         HIPCHK(hipMemcpyAsync(V.matches.p, matches + m_base, total * sizeof(VerifyMatch), hipMemcpyHostToDevice, st));
+    if (progressive && total) {
+        HIPCHK(hipMemcpyAsync(V.growth.p, V.h_growth.p, total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(V.rank_wgs.p, V.h_rank_wgs.p, n_wgs * sizeof(uint2), hipMemcpyHostToDevice, st));
+        if (quality)
+            HIPCHK(hipMemcpyAsync(V.quality.p, quality + m_base, total * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    const VerifyProgressive* pg = progressive ? &prog : nullptr;
     if (kind == VerifyKind::Fundamental)
         launch_verify_epipolar(d_kps + row_base, V.matches.p, V.pairs.p, (int)n_pairs, (uint32_t)total, prm->threshold,
                                prm->iterations, prm->seed, prm->refit_rounds, V.rec.p, V.box.p, V.models.p, V.best.p,
-                               V.out.p, V.mask.p, st);
+                               V.out.p, V.mask.p, st, pg);
     else
         launch_verify(d_kps + row_base, V.matches.p, V.pairs.p, (int)n_pairs, (uint32_t)total, prm->threshold,
                       prm->iterations, prm->seed, prm->refit_rounds, V.rec.p, V.models.p, V.best.p, V.out.p, V.mask.p,
-                      st);
+                      st, pg);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(models, V.out.p, (size_t)n_pairs * sizeof(VerifyModel), hipMemcpyDeviceToHost, st));
     if (total) HIPCHK(hipMemcpyAsync(inliers + m_base, V.mask.p, total, hipMemcpyDeviceToHost, st));
@@ -1298,18 +1341,20 @@ namespace {
 int verify_pairs_device(VerifyKind kind, sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets,
                         uint32_t n_segs, const sift_mi_seg_pair* pairs, uint32_t n_pairs, const sift_mi_match* matches,
                         const size_t* pair_offsets, const sift_mi_ransac_params* params, void* models,
-                        uint8_t* inliers) {
+                        uint8_t* inliers, VerifySampling sampling = VerifySampling::Uniform,
+                        const float* quality = nullptr) {
     if (!c || !d_kps || !offsets || !pairs || !matches || !pair_offsets || !params || !models || !inliers)
         return fail(SIFT_MI_EINVAL, "null argument");
     return match_guard([&]() -> int {
         return verify_run(c, kind, reinterpret_cast<const OutKp*>(d_kps), offsets, n_segs, pairs, n_pairs, matches,
-                          pair_offsets, params, models, inliers);
+                          pair_offsets, params, models, inliers, nullptr, nullptr, sampling, quality);
     });
 }
 
 int verify_matches(VerifyKind kind, sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
                    const sift_mi_keypoint* train_kps, size_t nt, const sift_mi_match* matches, size_t n_matches,
-                   const sift_mi_ransac_params* params, void* model, uint8_t* inliers) {
+                   const sift_mi_ransac_params* params, void* model, uint8_t* inliers,
+                   VerifySampling sampling = VerifySampling::Uniform, const float* quality = nullptr) {
     if (!c || !params || !model || (nq && !query_kps) || (nt && !train_kps) || (n_matches && (!matches || !inliers)))
         return fail(SIFT_MI_EINVAL, "null argument");
     if (nq > 0x7fffffff || nt > 0x7fffffff || nq + nt > 0x7fffffff)
@@ -1318,7 +1363,8 @@ int verify_matches(VerifyKind kind, sift_mi_ctx* c, const sift_mi_keypoint* quer
         const size_t offsets[3] = {0, nq, nq + nt}, po[2] = {0, n_matches};
         const sift_mi_seg_pair pair{0, 1};
         return verify_run(c, kind, nullptr, offsets, 2, &pair, 1, matches, po, params, model, inliers,
-                          reinterpret_cast<const OutKp*>(query_kps), reinterpret_cast<const OutKp*>(train_kps));
+                          reinterpret_cast<const OutKp*>(query_kps), reinterpret_cast<const OutKp*>(train_kps), sampling,
+                          quality);
     });
 }
 }  // namespace
@@ -1353,6 +1399,43 @@ int sift_mi_verify_matches_epipolar(sift_mi_ctx* c, const sift_mi_keypoint* quer
                                     uint8_t* inliers) {
     return verify_matches(VerifyKind::Fundamental, c, query_kps, nq, train_kps, nt, matches, n_matches, params, model,
                           inliers);
+}
+
+// the same with progressive (PROSAC) sampling: prosac_growth.h, DESIGN.md 3.18
+int sift_mi_verify_pairs_progressive_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps, const size_t* offsets,
+                                            uint32_t n_segs, const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                            const sift_mi_match* matches, const size_t* pair_offsets,
+                                            const float* quality, const sift_mi_ransac_params* params,
+                                            sift_mi_homography* models, uint8_t* inliers) {
+    return verify_pairs_device(VerifyKind::Homography, c, d_kps, offsets, n_segs, pairs, n_pairs, matches, pair_offsets,
+                               params, models, inliers, VerifySampling::Progressive, quality);
+}
+
+int sift_mi_verify_matches_progressive(sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
+                                       const sift_mi_keypoint* train_kps, size_t nt, const sift_mi_match* matches,
+                                       size_t n_matches, const float* quality, const sift_mi_ransac_params* params,
+                                       sift_mi_homography* model, uint8_t* inliers) {
+    return verify_matches(VerifyKind::Homography, c, query_kps, nq, train_kps, nt, matches, n_matches, params, model,
+                          inliers, VerifySampling::Progressive, quality);
+}
+
+int sift_mi_verify_pairs_epipolar_progressive_device(sift_mi_ctx* c, const sift_mi_keypoint* d_kps,
+                                                     const size_t* offsets, uint32_t n_segs,
+                                                     const sift_mi_seg_pair* pairs, uint32_t n_pairs,
+                                                     const sift_mi_match* matches, const size_t* pair_offsets,
+                                                     const float* quality, const sift_mi_ransac_params* params,
+                                                     sift_mi_fundamental* models, uint8_t* inliers) {
+    return verify_pairs_device(VerifyKind::Fundamental, c, d_kps, offsets, n_segs, pairs, n_pairs, matches,
+                               pair_offsets, params, models, inliers, VerifySampling::Progressive, quality);
+}
+
+int sift_mi_verify_matches_epipolar_progressive(sift_mi_ctx* c, const sift_mi_keypoint* query_kps, size_t nq,
+                                                const sift_mi_keypoint* train_kps, size_t nt,
+                                                const sift_mi_match* matches, size_t n_matches, const float* quality,
+                                                const sift_mi_ransac_params* params, sift_mi_fundamental* model,
+                                                uint8_t* inliers) {
+    return verify_matches(VerifyKind::Fundamental, c, query_kps, nq, train_kps, nt, matches, n_matches, params, model,
+                          inliers, VerifySampling::Progressive, quality);
 }
 
 // ---- feature tracks (labelled extension; tracks.hip) ---------------------------

@@ -309,6 +309,13 @@ struct VerifyScratch {
     DevBuf<unsigned long long> best;  // per pair (count << 32 | ~hypothesis)
     DevBuf<VerifyModel> out;
     DevBuf<uint8_t> mask;
+    // the progressive calls (sift_mi_verify_*_progressive*; prosac_growth.h)
+    DevBuf<float> quality;     // per match, when the caller passes one
+    DevBuf<uint32_t> growth;   // per match position its pair's T'
+    DevBuf<uint32_t> perm;     // per rank position the caller's match
+    DevBuf<uint2> rank_wgs;    // per workgroup of the ranking gather (pair, first match)
+    PinBuf<uint32_t> h_growth;
+    PinBuf<uint2> h_rank_wgs;
 };
 
 // Pooled scratch of the track builder (sift_mi_build_tracks_device): grows on

@@ -362,15 +362,32 @@ struct VerifyModel {
     uint32_t refits;
 };
 constexpr int kVerifyChunk = 1024;  // records of a pair in LDS at a time (k_verify_score)
+// Progressive (PROSAC) sampling (LABELLED EXTENSION; tests/prosac_ref.py is the
+// definition): the records are gathered in rank order and each
+// hypothesis draws from the best n_h of them.  Null where a launch takes one:
+// uniform sampling, the kernels and results of before.
+constexpr int kVerifyRankRows = 512;    // matches of a pair per workgroup of k_verify_gather_ranked
+constexpr int kVerifyRankStage = 1024;  // keys of a pair in LDS at a time
+struct VerifyProgressive {
+    const float* quality;    // [n_rec] finite, sign bit clear (the host checked); null: matches[i].distance
+    const uint32_t* growth;  // [n_rec] per pair its slice of the growth table (prosac_growth.h)
+    const uint2* wgs;        // [n_wgs] (pair, first match of the workgroup within it), kVerifyRankRows apart
+    uint32_t n_wgs;
+    uint32_t* perm;          // [n_rec] scratch: the caller's match (within its pair) at each rank
+};
 // matches[n_rec] hold indices the host has checked against their segments.
 // rec[n_rec], models[n_pairs * iterations * 9], best[n_pairs] are scratch;
 // out[n_pairs] and inliers[n_rec] the results.
 void launch_verify(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs, uint32_t n_rec,
                    float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds, float4* rec, float* models,
-                   unsigned long long* best, VerifyModel* out, uint8_t* inliers, hipStream_t st);
+                   unsigned long long* best, VerifyModel* out, uint8_t* inliers, hipStream_t st,
+                   const VerifyProgressive* prog = nullptr);
 
 void launch_verify_gather(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs,
                           uint32_t n_rec, float4* rec, hipStream_t st);
+// rec and prog.perm in rank order; the cost is the sum of m^2 key compares over the pairs
+void launch_verify_gather_ranked(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs,
+                                 const VerifyProgressive& prog, float4* rec, hipStream_t st);
 
 // verify_epipolar.hip
 // RANSAC fundamental matrix + eigen-refit of matched pairs (LABELLED
@@ -380,7 +397,7 @@ void launch_verify_gather(const OutKp* kps, const VerifyMatch* matches, const Ve
 void launch_verify_epipolar(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs,
                             uint32_t n_rec, float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds,
                             float4* rec, double* box, float* models, unsigned long long* best, VerifyModel* out,
-                            uint8_t* inliers, hipStream_t st);
+                            uint8_t* inliers, hipStream_t st, const VerifyProgressive* prog = nullptr);
 
 // tracks.hip
 // Feature tracks: connected components of the kept matches over the arena's

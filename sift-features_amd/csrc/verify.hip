@@ -18,6 +18,14 @@
 //                     the pair's slot with one 64-bit atomicMax
 //   k_verify_finish   one workgroup per pair: the winner's mask, the refit
 //                     rounds, the sift_mi_homography record
+//
+// The *_progressive calls (PROSAC; tests/prosac_ref.py) swap two
+// of them and leave the rest:
+//
+//   k_verify_gather_ranked  the gather, with the pair's records in the order of
+//                           their quality and perm[] back to the caller's matches
+//   k_verify_models_prog    k_verify_models' body with the progressive sample
+//   k_verify_finish         with perm: the mask in the caller's match order
 #include "verify_common.h"
 
 namespace siftmi {
@@ -94,16 +102,82 @@ __global__ __launch_bounds__(256) void k_verify_gather(const OutKp* __restrict__
     rec[i] = make_float4(q.x, q.y, t.x, t.y);
 }
 
-__global__ __launch_bounds__(256) void k_verify_models(const float4* __restrict__ rec,
-                                                       const VerifyPair* __restrict__ pairs, uint32_t seed,
-                                                       uint32_t iterations, uint32_t blocks_per_pair,
-                                                       float* __restrict__ models) {
+// The gather of the progressive calls: a pair's records in rank order.  Match i
+// has the key (u32 pattern of its quality << 32 | i), rank_i = #{j of the pair:
+// key_j < key_i}; the keys are distinct (the index is in them), so the ranks are
+// a permutation and one strict compare is the whole rule.  wgs[b] = (pair, first
+// match of workgroup b within it): no workgroup straddles a pair.  Each lane holds
+// kRankQ matches; the pair's keys pass through LDS kVerifyRankStage at a time,
+// every lane reading the same address (a broadcast), slots past the pair's end
+// hold all ones, which is below no key.  A rank is a count: no order of lanes or
+// stages can show, there is no atomic, and no lane reads a key outside its pair.
+// quality null: the matches' own distance.
+constexpr int kRankQ = 2;
+static_assert(kVerifyRankRows == 256 * kRankQ, "sift_kernels.h states the matches of a workgroup");
+static_assert(kVerifyRankStage % 256 == 0 && kVerifyRankStage % 4 == 0, "staging and the unrolled walk");
+
+__global__ __launch_bounds__(256) void k_verify_gather_ranked(const OutKp* __restrict__ kps,
+                                                              const VerifyMatch* __restrict__ matches,
+                                                              const VerifyPair* __restrict__ pairs,
+                                                              const uint2* __restrict__ wgs,
+                                                              const float* __restrict__ quality,
+                                                              float4* __restrict__ rec, uint32_t* __restrict__ perm) {
+    __shared__ unsigned long long s_key[kVerifyRankStage];
+    const uint2 wg = wgs[blockIdx.x];
+    const uint32_t t = threadIdx.x;
+    const VerifyPair P = pairs[wg.x];
+    const auto key_of = [&](uint32_t j) {  // j < P.m
+        const float v = quality ? quality[(size_t)P.rec0 + j] : matches[(size_t)P.rec0 + j].distance;
+        return ((unsigned long long)__float_as_uint(v) << 32) | j;
+    };
+    unsigned long long key[kRankQ];
+    uint32_t rank[kRankQ];
+#pragma unroll
+    for (int q = 0; q < kRankQ; q++) {
+        const uint32_t i = wg.y + (uint32_t)q * 256u + t;
+        key[q] = i < P.m ? key_of(i) : 0ull;  // a lane past the pair's end: nothing is stored
+        rank[q] = 0;
+    }
+    for (uint32_t base = 0; base < P.m; base += kVerifyRankStage) {
+        const uint32_t cnt = min((uint32_t)kVerifyRankStage, P.m - base);
+        __syncthreads();  // the walk over the previous stage is over
+#pragma unroll
+        for (uint32_t k = t; k < (uint32_t)kVerifyRankStage; k += 256u) s_key[k] = k < cnt ? key_of(base + k) : ~0ull;
+        __syncthreads();
+        const uint32_t lim = (cnt + 3u) & ~3u;
+#pragma unroll 4
+        for (uint32_t k = 0; k < lim; k++) {
+            const unsigned long long v = s_key[k];
+#pragma unroll
+            for (int q = 0; q < kRankQ; q++) rank[q] += v < key[q] ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kRankQ; q++) {
+        const uint32_t i = wg.y + (uint32_t)q * 256u + t;
+        if (i >= P.m) continue;
+        const VerifyMatch mt = matches[(size_t)P.rec0 + i];
+        const OutKp a = kps[(size_t)P.qrow0 + (uint32_t)mt.query_idx];
+        const OutKp b = kps[(size_t)P.trow0 + (uint32_t)mt.train_idx];
+        rec[(size_t)P.rec0 + rank[q]] = make_float4(a.x, a.y, b.x, b.y);
+        perm[(size_t)P.rec0 + rank[q]] = i;
+    }
+}
+
+// kProgressive: the sample comes from the growth table's slice of the pair
+// (vfy::sample_progressive) over records in rank order; a compile-time choice,
+// so the uniform kernel's code is what it was.
+template <bool kProgressive>
+__device__ __forceinline__ void models_body(const float4* __restrict__ rec, const VerifyPair* __restrict__ pairs,
+                                            const uint32_t* __restrict__ growth, uint32_t seed, uint32_t iterations,
+                                            uint32_t blocks_per_pair, float* __restrict__ models) {
     const uint32_t p = blockIdx.x / blocks_per_pair;
     const uint32_t h = (blockIdx.x % blocks_per_pair) * 256u + threadIdx.x;
     const VerifyPair P = pairs[p];
     if (h >= iterations || P.m < 4) return;
     uint32_t pick[4];
-    vfy::sample_distinct<4>(seed, h, P.m, pick);
+    if constexpr (kProgressive) vfy::sample_progressive<4>(seed, h, P.m, growth + P.rec0, pick);
+    else vfy::sample_distinct<4>(seed, h, P.m, pick);
     double x[4], y[4], X[4], Y[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -139,6 +213,21 @@ __global__ __launch_bounds__(256) void k_verify_models(const float4* __restrict_
     for (int k = 0; k < 9; k++) out[k] = valid ? hf[k] : 0.0f;
 }
 
+__global__ __launch_bounds__(256) void k_verify_models(const float4* __restrict__ rec,
+                                                       const VerifyPair* __restrict__ pairs, uint32_t seed,
+                                                       uint32_t iterations, uint32_t blocks_per_pair,
+                                                       float* __restrict__ models) {
+    models_body<false>(rec, pairs, nullptr, seed, iterations, blocks_per_pair, models);
+}
+
+__global__ __launch_bounds__(256) void k_verify_models_prog(const float4* __restrict__ rec,
+                                                            const VerifyPair* __restrict__ pairs,
+                                                            const uint32_t* __restrict__ growth, uint32_t seed,
+                                                            uint32_t iterations, uint32_t blocks_per_pair,
+                                                            float* __restrict__ models) {
+    models_body<true>(rec, pairs, growth, seed, iterations, blocks_per_pair, models);
+}
+
 __global__ __launch_bounds__(256) void k_verify_score(const float4* __restrict__ rec,
                                                       const VerifyPair* __restrict__ pairs,
                                                       const float* __restrict__ models, uint32_t iterations,
@@ -156,7 +245,8 @@ __global__ __launch_bounds__(256) void k_verify_finish(const float4* __restrict_
                                                        const float* __restrict__ models, uint32_t iterations,
                                                        float thr, uint32_t refit_rounds,
                                                        const unsigned long long* __restrict__ best,
-                                                       VerifyModel* __restrict__ out, uint8_t* __restrict__ inliers) {
+                                                       VerifyModel* __restrict__ out, uint8_t* __restrict__ inliers,
+                                                       const uint32_t* __restrict__ perm) {
     __shared__ float s_box[4][8];
     __shared__ double s_sum[4][kVerifySums];
     __shared__ double s_A[8][9];
@@ -167,8 +257,11 @@ __global__ __launch_bounds__(256) void k_verify_finish(const float4* __restrict_
     const uint64_t key = best[p];
     const float4* __restrict__ r = rec + P.rec0;
     uint8_t* __restrict__ mask = inliers + P.rec0;
+    // the mask byte of record i: with perm (records in rank order) the caller's match perm[i]
+    const uint32_t* __restrict__ pm = perm ? perm + P.rec0 : nullptr;
+    const auto at = [pm](uint32_t i) { return pm ? pm[i] : i; };
     if (P.m < 4 || key == 0) {  // no model
-        for (uint32_t i = tid; i < P.m; i += 256u) mask[i] = 0;
+        for (uint32_t i = tid; i < P.m; i += 256u) mask[at(i)] = 0;
         if (tid == 0) {
             VerifyModel o;
 #pragma unroll
@@ -188,7 +281,7 @@ __global__ __launch_bounds__(256) void k_verify_finish(const float4* __restrict_
 #pragma unroll
     for (int k = 0; k < 9; k++) h[k] = models[((size_t)p * iterations + bh) * 9 + k];
     // lane tid owns matches tid, tid + 256, ...: it alone reads and writes their mask bytes
-    for (uint32_t i = tid; i < P.m; i += 256u) mask[i] = inlier(h, r[i], t2) ? 1 : 0;
+    for (uint32_t i = tid; i < P.m; i += 256u) mask[at(i)] = inlier(h, r[i], t2) ? 1 : 0;
 
     if (refit_rounds) {
         // box normalisation over all the pair's matches: min / max are exact in any order
@@ -233,7 +326,7 @@ __global__ __launch_bounds__(256) void k_verify_finish(const float4* __restrict_
 #pragma unroll
             for (int k = 0; k < kVerifySums; k++) S[k] = 0.0;
             for (uint32_t i = tid; i < P.m; i += 256u) {
-                if (!mask[i]) continue;
+                if (!mask[at(i)]) continue;
                 const float4 v = r[i];
                 const double x = ((double)v.x - cx) * sq, y = ((double)v.y - cy) * sq;
                 const double X = ((double)v.z - CX) * st, Y = ((double)v.w - CY) * st;
@@ -328,7 +421,7 @@ __global__ __launch_bounds__(256) void k_verify_finish(const float4* __restrict_
             for (uint32_t i = tid; i < P.m; i += 256u) {
                 const int in = inlier(h2, r[i], t2) ? 1 : 0;
                 cnt += in;
-                chg += in != (int)mask[i];
+                chg += in != (int)mask[at(i)];
             }
             cnt = wave_sum(cnt);
             chg = wave_sum(chg);
@@ -341,7 +434,7 @@ __global__ __launch_bounds__(256) void k_verify_finish(const float4* __restrict_
             const bool changed = (s_chg[0] + s_chg[1] + s_chg[2] + s_chg[3]) != 0;
             __syncthreads();  // s_cnt / s_chg / s_h / s_sum are rewritten by the next round
             if (n2 < n_in) break;  // rejected: the count dropped
-            for (uint32_t i = tid; i < P.m; i += 256u) mask[i] = inlier(h2, r[i], t2) ? 1 : 0;
+            for (uint32_t i = tid; i < P.m; i += 256u) mask[at(i)] = inlier(h2, r[i], t2) ? 1 : 0;
 #pragma unroll
             for (int k = 0; k < 9; k++) h[k] = h2[k];
             n_in = n2;
@@ -367,21 +460,34 @@ void launch_verify_gather(const OutKp* kps, const VerifyMatch* matches, const Ve
                        n_rec, rec);
 }
 
+void launch_verify_gather_ranked(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs,
+                                 const VerifyProgressive& prog, float4* rec, hipStream_t st) {
+    hipLaunchKernelGGL(k_verify_gather_ranked, dim3(prog.n_wgs), dim3(256), 0, st, kps, matches, pairs, prog.wgs,
+                       prog.quality, rec, prog.perm);
+}
+
 void launch_verify(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs, uint32_t n_rec,
                    float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds, float4* rec, float* models,
-                   unsigned long long* best, VerifyModel* out, uint8_t* inliers, hipStream_t st) {
+                   unsigned long long* best, VerifyModel* out, uint8_t* inliers, hipStream_t st,
+                   const VerifyProgressive* prog) {
     if (n_pairs <= 0) return;
     const uint32_t bpp = (iterations + 255u) / 256u;
     (void)hipMemsetAsync(best, 0, (size_t)n_pairs * 8, st);
     if (n_rec) {
-        launch_verify_gather(kps, matches, pairs, n_pairs, n_rec, rec, st);
-        hipLaunchKernelGGL(k_verify_models, dim3((uint32_t)n_pairs * bpp), dim3(256), 0, st, rec, pairs, seed, iterations,
-                           bpp, models);
+        if (prog) {
+            launch_verify_gather_ranked(kps, matches, pairs, *prog, rec, st);
+            hipLaunchKernelGGL(k_verify_models_prog, dim3((uint32_t)n_pairs * bpp), dim3(256), 0, st, rec, pairs,
+                               prog->growth, seed, iterations, bpp, models);
+        } else {
+            launch_verify_gather(kps, matches, pairs, n_pairs, n_rec, rec, st);
+            hipLaunchKernelGGL(k_verify_models, dim3((uint32_t)n_pairs * bpp), dim3(256), 0, st, rec, pairs, seed,
+                               iterations, bpp, models);
+        }
         hipLaunchKernelGGL(k_verify_score, dim3((uint32_t)n_pairs * bpp), dim3(256), 0, st, rec, pairs, models,
                            iterations, bpp, thr, best);
     }
     hipLaunchKernelGGL(k_verify_finish, dim3((uint32_t)n_pairs), dim3(256), 0, st, rec, pairs, models, iterations, thr,
-                       refit_rounds, best, out, inliers);
+                       refit_rounds, best, out, inliers, (const uint32_t*)(prog && n_rec ? prog->perm : nullptr));
 }
 
 }  // namespace siftmi

@@ -41,6 +41,32 @@ __device__ __forceinline__ void sample_distinct(uint32_t seed, uint32_t h, uint3
     }
 }
 
+// The progressive (PROSAC) sample of hypothesis h over a pair's m >= N records
+// in rank order (tests/prosac_ref.py).  tab is the pair's slice
+// of the growth table (csrc/prosac_growth.h): T'_{i + 1} at position i >= N - 1,
+// ascending.  The first position i in [N - 1, m) with h < tab[i] gives n_h = i +
+// 1: N - 1 distinct draws below i, then record i as the last member.  Without
+// one (the tail, when m is close to N) the uniform draw over all m.
+template <int N>
+__device__ __forceinline__ void sample_progressive(uint32_t seed, uint32_t h, uint32_t m,
+                                                   const uint32_t* __restrict__ tab, uint32_t (&pick)[N]) {
+    uint32_t lo = N - 1, hi = m;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (h < tab[mid]) hi = mid;
+        else lo = mid + 1;
+    }
+    if (lo < m) {
+        uint32_t head[N - 1];
+        sample_distinct<N - 1>(seed, h, lo, head);
+#pragma unroll
+        for (int k = 0; k < N - 1; k++) pick[k] = head[k];
+        pick[N - 1] = lo;
+    } else {
+        sample_distinct<N>(seed, h, m, pick);
+    }
+}
+
 __device__ __forceinline__ bool finite9(const float (&h)[9]) {
     bool ok = true;
 #pragma unroll

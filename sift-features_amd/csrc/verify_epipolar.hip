@@ -24,6 +24,11 @@
 //                       rounds (45 sums, cyclic Jacobi on the 9 x 9 in LDS
 //                       spread over nine lanes, rank 2), the sift_mi_fundamental
 //                       record
+//
+// The *_progressive calls (PROSAC; tests/prosac_ref.py) run
+// verify.hip's ranking gather in place of its gather, k_verify_models_f_prog
+// (this kernel's body with the progressive sample) and k_verify_finish_f with
+// perm, which writes the mask in the caller's match order.
 #include "verify_common.h"
 
 namespace siftmi {
@@ -197,11 +202,14 @@ __global__ __launch_bounds__(256) void k_verify_box_f(const float4* __restrict__
     o[5] = 2.0 / fmax(fmax(dhi[2] - dlo[2], dhi[3] - dlo[3]), 1.0);
 }
 
-__global__ __launch_bounds__(kModelLanes) void k_verify_models_f(const float4* __restrict__ rec,
-                                                                 const VerifyPair* __restrict__ pairs,
-                                                                 const double* __restrict__ box, uint32_t seed,
-                                                                 uint32_t iterations, uint32_t blocks_per_pair,
-                                                                 float* __restrict__ models) {
+// kProgressive: the sample comes from the growth table's slice of the pair
+// (vfy::sample_progressive) over records in rank order; a compile-time choice,
+// so the uniform kernel's code is what it was.
+template <bool kProgressive>
+__device__ __forceinline__ void models_f_body(const float4* __restrict__ rec, const VerifyPair* __restrict__ pairs,
+                                              const double* __restrict__ box, const uint32_t* __restrict__ growth,
+                                              uint32_t seed, uint32_t iterations, uint32_t blocks_per_pair,
+                                              float* __restrict__ models) {
     // the lane's 8 x 9 system, entry e = 9 r + c at s_a[e][lane]: the bank depends on
     // the lane only, so any per-lane (data-dependent) entry index is conflict-free
     __shared__ double s_a[72][kModelLanes];
@@ -213,7 +221,8 @@ __global__ __launch_bounds__(kModelLanes) void k_verify_models_f(const float4* _
     const Box B = {bp[0], bp[1], bp[2], bp[3], bp[4], bp[5]};
 #define A_(r, c) s_a[(r) * 9 + (c)][lane]
     uint32_t pick[8];
-    vfy::sample_distinct<8>(seed, h, P.m, pick);
+    if constexpr (kProgressive) vfy::sample_progressive<8>(seed, h, P.m, growth + P.rec0, pick);
+    else vfy::sample_distinct<8>(seed, h, P.m, pick);
 #pragma unroll
     for (int i = 0; i < 8; i++) {
         const float4 v = rec[(size_t)P.rec0 + pick[i]];
@@ -301,6 +310,24 @@ __global__ __launch_bounds__(kModelLanes) void k_verify_models_f(const float4* _
     for (int k = 0; k < 9; k++) out[k] = valid ? hf[k] : 0.0f;
 }
 
+__global__ __launch_bounds__(kModelLanes) void k_verify_models_f(const float4* __restrict__ rec,
+                                                                 const VerifyPair* __restrict__ pairs,
+                                                                 const double* __restrict__ box, uint32_t seed,
+                                                                 uint32_t iterations, uint32_t blocks_per_pair,
+                                                                 float* __restrict__ models) {
+    models_f_body<false>(rec, pairs, box, nullptr, seed, iterations, blocks_per_pair, models);
+}
+
+__global__ __launch_bounds__(kModelLanes) void k_verify_models_f_prog(const float4* __restrict__ rec,
+                                                                      const VerifyPair* __restrict__ pairs,
+                                                                      const double* __restrict__ box,
+                                                                      const uint32_t* __restrict__ growth,
+                                                                      uint32_t seed, uint32_t iterations,
+                                                                      uint32_t blocks_per_pair,
+                                                                      float* __restrict__ models) {
+    models_f_body<true>(rec, pairs, box, growth, seed, iterations, blocks_per_pair, models);
+}
+
 __global__ __launch_bounds__(256) void k_verify_score_f(const float4* __restrict__ rec,
                                                         const VerifyPair* __restrict__ pairs,
                                                         const float* __restrict__ models, uint32_t iterations,
@@ -319,7 +346,8 @@ __global__ __launch_bounds__(256) void k_verify_finish_f(const float4* __restric
                                                          const double* __restrict__ box, uint32_t iterations,
                                                          float thr, uint32_t refit_rounds,
                                                          const unsigned long long* __restrict__ best,
-                                                         VerifyModel* __restrict__ out, uint8_t* __restrict__ inliers) {
+                                                         VerifyModel* __restrict__ out, uint8_t* __restrict__ inliers,
+                                                         const uint32_t* __restrict__ perm) {
     __shared__ double s_sum[4][kEpipolarSums];
     __shared__ double s_J[81], s_V[81];
     __shared__ float s_f[9];
@@ -329,8 +357,11 @@ __global__ __launch_bounds__(256) void k_verify_finish_f(const float4* __restric
     const uint64_t key = best[p];
     const float4* __restrict__ r = rec + P.rec0;
     uint8_t* __restrict__ mask = inliers + P.rec0;
+    // the mask byte of record i: with perm (records in rank order) the caller's match perm[i]
+    const uint32_t* __restrict__ pm = perm ? perm + P.rec0 : nullptr;
+    const auto at = [pm](uint32_t i) { return pm ? pm[i] : i; };
     if (P.m < 8 || key == 0) {  // no model
-        for (uint32_t i = tid; i < P.m; i += 256u) mask[i] = 0;
+        for (uint32_t i = tid; i < P.m; i += 256u) mask[at(i)] = 0;
         if (tid == 0) {
             VerifyModel o;
 #pragma unroll
@@ -350,7 +381,7 @@ __global__ __launch_bounds__(256) void k_verify_finish_f(const float4* __restric
 #pragma unroll
     for (int k = 0; k < 9; k++) f[k] = models[((size_t)p * iterations + bh) * 9 + k];
     // lane tid owns matches tid, tid + 256, ...: it alone reads and writes their mask bytes
-    for (uint32_t i = tid; i < P.m; i += 256u) mask[i] = FundamentalModel::inlier(f, r[i], t2) ? 1 : 0;
+    for (uint32_t i = tid; i < P.m; i += 256u) mask[at(i)] = FundamentalModel::inlier(f, r[i], t2) ? 1 : 0;
 
     if (refit_rounds) {
         const double* bp = box + (size_t)p * 6;
@@ -362,7 +393,7 @@ __global__ __launch_bounds__(256) void k_verify_finish_f(const float4* __restric
 #pragma unroll
             for (int k = 0; k < kEpipolarSums; k++) S[k] = 0.0;
             for (uint32_t i = tid; i < P.m; i += 256u) {
-                if (!mask[i]) continue;
+                if (!mask[at(i)]) continue;
                 const float4 v = r[i];
                 const double x = ((double)v.x - B.cx) * B.sq, y = ((double)v.y - B.cy) * B.sq;
                 const double X = ((double)v.z - B.CX) * B.st, Y = ((double)v.w - B.CY) * B.st;
@@ -431,7 +462,7 @@ __global__ __launch_bounds__(256) void k_verify_finish_f(const float4* __restric
             for (uint32_t i = tid; i < P.m; i += 256u) {
                 const int in = FundamentalModel::inlier(f2, r[i], t2) ? 1 : 0;
                 cnt += in;
-                chg += in != (int)mask[i];
+                chg += in != (int)mask[at(i)];
             }
             cnt = wave_sum(cnt);
             chg = wave_sum(chg);
@@ -444,7 +475,7 @@ __global__ __launch_bounds__(256) void k_verify_finish_f(const float4* __restric
             const bool changed = (s_chg[0] + s_chg[1] + s_chg[2] + s_chg[3]) != 0;
             __syncthreads();  // s_cnt / s_chg / s_f / s_sum / s_J are rewritten by the next round
             if (n2 < n_in) break;  // rejected: the count dropped
-            for (uint32_t i = tid; i < P.m; i += 256u) mask[i] = FundamentalModel::inlier(f2, r[i], t2) ? 1 : 0;
+            for (uint32_t i = tid; i < P.m; i += 256u) mask[at(i)] = FundamentalModel::inlier(f2, r[i], t2) ? 1 : 0;
 #pragma unroll
             for (int k = 0; k < 9; k++) f[k] = f2[k];
             n_in = n2;
@@ -467,20 +498,25 @@ __global__ __launch_bounds__(256) void k_verify_finish_f(const float4* __restric
 void launch_verify_epipolar(const OutKp* kps, const VerifyMatch* matches, const VerifyPair* pairs, int n_pairs,
                             uint32_t n_rec, float thr, uint32_t iterations, uint32_t seed, uint32_t refit_rounds,
                             float4* rec, double* box, float* models, unsigned long long* best, VerifyModel* out,
-                            uint8_t* inliers, hipStream_t st) {
+                            uint8_t* inliers, hipStream_t st, const VerifyProgressive* prog) {
     if (n_pairs <= 0) return;
     const uint32_t bpp = (iterations + 255u) / 256u, bpp_m = (iterations + kModelLanes - 1u) / kModelLanes;
     (void)hipMemsetAsync(best, 0, (size_t)n_pairs * 8, st);
     if (n_rec) {
-        launch_verify_gather(kps, matches, pairs, n_pairs, n_rec, rec, st);
+        if (prog) launch_verify_gather_ranked(kps, matches, pairs, *prog, rec, st);
+        else launch_verify_gather(kps, matches, pairs, n_pairs, n_rec, rec, st);
         hipLaunchKernelGGL(k_verify_box_f, dim3((uint32_t)n_pairs), dim3(256), 0, st, rec, pairs, box);
-        hipLaunchKernelGGL(k_verify_models_f, dim3((uint32_t)n_pairs * bpp_m), dim3(kModelLanes), 0, st, rec, pairs, box,
-                           seed, iterations, bpp_m, models);
+        if (prog)
+            hipLaunchKernelGGL(k_verify_models_f_prog, dim3((uint32_t)n_pairs * bpp_m), dim3(kModelLanes), 0, st, rec,
+                               pairs, box, prog->growth, seed, iterations, bpp_m, models);
+        else
+            hipLaunchKernelGGL(k_verify_models_f, dim3((uint32_t)n_pairs * bpp_m), dim3(kModelLanes), 0, st, rec, pairs,
+                               box, seed, iterations, bpp_m, models);
         hipLaunchKernelGGL(k_verify_score_f, dim3((uint32_t)n_pairs * bpp), dim3(256), 0, st, rec, pairs, models,
                            iterations, bpp, thr, best);
     }
     hipLaunchKernelGGL(k_verify_finish_f, dim3((uint32_t)n_pairs), dim3(256), 0, st, rec, pairs, models, box, iterations,
-                       thr, refit_rounds, best, out, inliers);
+                       thr, refit_rounds, best, out, inliers, (const uint32_t*)(prog && n_rec ? prog->perm : nullptr));
 }
 
 }  // namespace siftmi

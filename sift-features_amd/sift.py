@@ -487,16 +487,46 @@ class Context:
         return np.array(values[:], np.float32).reshape(3, 3), mask.astype(bool), info
 
     @staticmethod
-    def _verify_model(model):
-        """The record type and the two entry points of `model`."""
+    def _verify_model(model, sampling="uniform"):
+        """The record type and the two entry points of `model` under `sampling`."""
+        if sampling not in ("uniform", "progressive"):
+            raise ValueError(f"sampling must be 'uniform' or 'progressive', not {sampling!r}")
+        prog = sampling == "progressive"
         if model == "homography":
+            if prog:
+                return (_lib.Homography, lib().sift_mi_verify_pairs_progressive_device,
+                        lib().sift_mi_verify_matches_progressive)
             return _lib.Homography, lib().sift_mi_verify_pairs_device, lib().sift_mi_verify_matches
         if model == "fundamental":
+            if prog:
+                return (_lib.Fundamental, lib().sift_mi_verify_pairs_epipolar_progressive_device,
+                        lib().sift_mi_verify_matches_epipolar_progressive)
             return _lib.Fundamental, lib().sift_mi_verify_pairs_epipolar_device, lib().sift_mi_verify_matches_epipolar
         raise ValueError(f"model must be 'homography' or 'fundamental', not {model!r}")
 
+    @staticmethod
+    def _quality_args(sampling, quality, po):
+        """The extra arguments of a progressive call: (the f32 array to keep
+        alive, [its pointer]); nothing for a uniform one.  `quality`: one array
+        per pair (or None for all: the matches' distance)."""
+        if sampling != "progressive":
+            if quality is not None:
+                raise ValueError("quality is only read with sampling='progressive'")
+            return None, []
+        if quality is None:
+            return None, [None]
+        if len(quality) != len(po) - 1:
+            raise ValueError("one quality array per pair")
+        q = np.zeros(max(int(po[-1]), 1), np.float32)
+        for p, v in enumerate(quality):
+            v = np.asarray(v, np.float32).reshape(-1)
+            if len(v) != po[p + 1] - po[p]:
+                raise ValueError("one quality per match")
+            q[po[p]:po[p + 1]] = v
+        return q, [q.ctypes.data]
+
     def verify_pairs_device(self, d_kps_ptr, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0,
-                            refit_rounds=2, model="homography"):
+                            refit_rounds=2, model="homography", sampling="uniform", quality=None):
         """LABELLED EXTENSION (the crate has nothing like it): per pair a RANSAC
         homography on its matches with up to `refit_rounds` least-squares
         refits on the inliers (sift_mi_verify_pairs_device; the rules are
@@ -516,9 +546,19 @@ class Context:
         keypoint (x, y) and its train keypoint (X, Y), largest entry 1.  F is
         rank 2 (up to f32 rounding) iff info["refits"] >= 1, the raw 8-point
         solution otherwise; a pair needs 8 matches.  A planar scene satisfies
-        a family of F (use the homography there), and 1024 hypotheses suit
-        inlier shares >= 0.5.  Any other `model` raises ValueError."""
-        record, call, _ = self._verify_model(model)
+        a family of F (use the homography there), and under uniform sampling
+        1024 hypotheses suit inlier shares >= 0.5.  Any other `model` raises
+        ValueError.
+
+        sampling="progressive" (a further labelled extension; PROSAC, the rule
+        is tests/prosac_ref.py's) ranks each pair's matches by `quality`, one
+        array per pair, lower is better, finite with the sign bit clear (None:
+        the matches' distance), and hypothesis h draws from the best n_h of
+        them, n_h growing with h (sift_mi_verify_pairs_progressive_device /
+        ..._epipolar_progressive_device); it reaches lower inlier shares with
+        the same `iterations`.  The masks stay in the matches' order.
+        sampling="uniform" is the call and the result of before."""
+        record, call, _ = self._verify_model(model, sampling)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         if offs.ndim != 1 or len(offs) < 1 or (offs < 0).any():
             raise ValueError("offsets: n_segs + 1 non-negative row numbers")
@@ -532,39 +572,42 @@ class Context:
         models = (record * max(len(pr), 1))()
         mask = np.zeros(max(int(po[-1]), 1), np.uint8)
         prm = self._ransac(threshold, iterations, seed, refit_rounds)
+        _q, extra = self._quality_args(sampling, quality, po)
         check(call(self._h, ctypes.c_void_p(d_kps_ptr), c_offs, len(offs) - 1, c_pairs, len(pr), rec.ctypes.data, c_po,
-                   ctypes.byref(prm), models, mask.ctypes.data))
+                   *extra, ctypes.byref(prm), models, mask.ctypes.data))
         return [self._verify_result(models[p], mask[po[p]:po[p + 1]]) for p in range(len(pr))]
 
     def verify_frames(self, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
-                      model="homography"):
+                      model="homography", sampling="uniform", quality=None):
         """verify_pairs_device on the keypoints the last
         sift_batch_device(..., fetch=False) left in HBM, e.g. on what
         match_frames(offsets, pairs, ...) returned."""
-        self._verify_model(model)
+        self._verify_model(model, sampling)
         d_kps, _, n = self.device_results()
         if int(offsets[-1]) > n:
             raise ValueError("offsets reach beyond the device results")
         return self.verify_pairs_device(d_kps, offsets, pairs, matches, threshold, iterations, seed, refit_rounds,
-                                        model=model)
+                                        model=model, sampling=sampling, quality=quality)
 
     def verify_matches(self, kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
-                       model="homography"):
+                       model="homography", sampling="uniform", quality=None):
         """The one-pair form on host keypoints (sift_mi_verify_matches): kps_q /
         kps_t are (n, 5) f32 keypoint arrays (SiftResult.keypoints_array; only
         x, y are read), matches one (query_idx, train_idx, distance) triple.
         Returns (H, inlier mask, info) as verify_pairs_device does per pair,
         (F, inlier mask, info) with model="fundamental"
-        (sift_mi_verify_matches_epipolar)."""
-        record, _, call = self._verify_model(model)
+        (sift_mi_verify_matches_epipolar).  sampling="progressive": as
+        verify_pairs_device, `quality` one array over the matches or None."""
+        record, _, call = self._verify_model(model, sampling)
         q = np.ascontiguousarray(kps_q, dtype=np.float32).reshape(-1, 5)
         t = np.ascontiguousarray(kps_t, dtype=np.float32).reshape(-1, 5)
         rec, po = self._match_records([matches])
         out = record()
         mask = np.zeros(max(int(po[-1]), 1), np.uint8)
         prm = self._ransac(threshold, iterations, seed, refit_rounds)
+        _q, extra = self._quality_args(sampling, None if quality is None else [quality], po)
         check(call(self._h, q.ctypes.data, len(q), t.ctypes.data, len(t), rec.ctypes.data, int(po[-1]),
-                   ctypes.byref(prm), ctypes.byref(out), mask.ctypes.data))
+                   *extra, ctypes.byref(prm), ctypes.byref(out), mask.ctypes.data))
         return self._verify_result(out, mask[:po[-1]])
 
     # -- guided matching (LABELLED EXTENSION: not in the crate) ----------------
@@ -1051,22 +1094,25 @@ def match_frames(offsets, pairs, ratio=None, cross_check=True):
 
 
 def verify_pairs_device(d_kps_ptr, offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
-                        model="homography"):
+                        model="homography", sampling="uniform", quality=None):
     """LABELLED EXTENSION: Context.verify_pairs_device on the default context."""
     return default_context().verify_pairs_device(d_kps_ptr, offsets, pairs, matches, threshold, iterations, seed,
-                                                 refit_rounds, model)
+                                                 refit_rounds, model, sampling, quality)
 
 
 def verify_frames(offsets, pairs, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2,
-                  model="homography"):
+                  model="homography", sampling="uniform", quality=None):
     """LABELLED EXTENSION: Context.verify_frames on the default context (its
     last sift_batch_device(..., fetch=False) results)."""
-    return default_context().verify_frames(offsets, pairs, matches, threshold, iterations, seed, refit_rounds, model)
+    return default_context().verify_frames(offsets, pairs, matches, threshold, iterations, seed, refit_rounds, model,
+                                           sampling, quality)
 
 
-def verify_matches(kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2, model="homography"):
+def verify_matches(kps_q, kps_t, matches, threshold=3.0, iterations=1024, seed=0, refit_rounds=2, model="homography",
+                   sampling="uniform", quality=None):
     """LABELLED EXTENSION: Context.verify_matches on the default context."""
-    return default_context().verify_matches(kps_q, kps_t, matches, threshold, iterations, seed, refit_rounds, model)
+    return default_context().verify_matches(kps_q, kps_t, matches, threshold, iterations, seed, refit_rounds, model,
+                                            sampling, quality)
 
 
 def match_pairs_guided_device(d_desc_ptr, d_kps_ptr, offsets, pairs, models, threshold=3.0, model="homography",

@@ -2,7 +2,8 @@
 MI355X path.
 
     python sift-features_amd/sift_match.py <a.jpg> <b.jpg> [--ratio R] [--verify [THR]]
-                                           [--model homography|fundamental] [--guided] [--spread N]
+                                           [--model homography|fundamental] [--progressive] [--guided]
+                                           [--spread N]
                                            [--processing opencv|imageproc] [--device N]
 
 examples/sift-match.rs:30-35, :87-97 opens two images, runs `sift()` on each and
@@ -18,6 +19,9 @@ RANSAC homography to the matches (verify.hip, the defaults of
 Context.verify_matches) and prints a fourth line with its inlier count;
 with `--model fundamental` (only read with --verify) it fits a RANSAC
 fundamental matrix instead (verify_epipolar.hip; THR is the Sampson distance).
+`--progressive` (only read with --verify), a labelled extension too, draws the
+RANSAC samples in the order of the matches' descriptor distance (PROSAC:
+Context.verify_matches(sampling="progressive")) and says so on the fourth line.
 `--guided` (only read with --verify), a further labelled extension, matches
 the pair again under the fitted model (match_guided.hip, the defaults of
 Context.match_guided: cross check, no ratio test, no distance cap, the
@@ -45,6 +49,7 @@ def main(argv=None):
     ap.add_argument("--ratio", type=float, default=None)
     ap.add_argument("--verify", type=float, nargs="?", const=3.0, default=None, metavar="THR")
     ap.add_argument("--model", choices=["homography", "fundamental"], default="homography")
+    ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--guided", action="store_true")
     ap.add_argument("--spread", type=int, default=None, metavar="N")
     ap.add_argument("--processing", choices=("imageproc", "opencv"), default="imageproc")
@@ -66,7 +71,8 @@ def main(argv=None):
             kps_a, desc_a, kps_b, desc_b = kps_a[rows_a], desc_a[rows_a], kps_b[rows_b], desc_b[rows_b]
         qi, ti, dist = ctx.match_descriptors(desc_b, desc_a, cross_check=True, ratio=a.ratio)
         if a.verify is not None:
-            g, _, info = ctx.verify_matches(kps_b, kps_a, (qi, ti, dist), threshold=a.verify, model=a.model)
+            g, _, info = ctx.verify_matches(kps_b, kps_a, (qi, ti, dist), threshold=a.verify, model=a.model,
+                                            sampling="progressive" if a.progressive else "uniform")
             if a.guided:
                 guided = ctx.match_guided(desc_b, kps_b, desc_a, kps_a, g, threshold=a.verify, model=a.model)
         if a.spread is not None:  # back to the rows of the two extractions
@@ -81,7 +87,8 @@ def main(argv=None):
         print(f"{len(rows_a)} and {len(rows_b)} kept (spread {a.spread})")
     print(f"{len(qi)} matches" + (f" (ratio {a.ratio:g})" if a.ratio is not None else ""))
     if a.verify is not None:
-        print(f"{info['n_inliers']} inliers ({a.model}, threshold {a.verify:g})")
+        print(f"{info['n_inliers']} inliers ({a.model}, threshold {a.verify:g}" +
+              (", progressive)" if a.progressive else ")"))
         if a.guided:
             print(f"{len(guided[0])} guided matches")
     return 0
